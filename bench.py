@@ -9,8 +9,11 @@ of the sampler = one full forward over condition+denoise tokens (the reference r
 everything every step, LVM/scheduler.py:174) + x1->v + CFG + update, replayed from a hipGraph.
 metric = denoised clip-tokens/sec = G*N*steps / time (whole job: summed over ranks; replicas only,
 each rank samples its own clip — weak scaling, no data-path collective).
+A plain run sets up, warms up, times the steps and prints the line; --full adds, as separate legs after the timed steps,
+the box calibration, the per-kernel roofline and vendor yardstick, the stage-1 training and VAE legs and the CPU baseline.
+--dump-outputs DIR writes the latents the timed steps returned (rank 0) as DIR/latents.npy (float32).
 
-  python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -454,10 +457,17 @@ def main():
                     help="vae / pipeline workloads: arithmetic of the 3x3 convolutions (video-gpt_amd/vae.py)")
     ap.add_argument("--breakdown", action="store_true", help="add per-operator HIP-event times of one eager denoise step")
     ap.add_argument("--rounds", type=int, default=1, help="pipeline workload: chained next-clip rounds (cfg-5 uses 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="infer workload: also run the calibration, roofline, stage-1, VAE and CPU-baseline legs (off: the "
+                         "timed denoise steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="infer workload: write what the last timed step returned (the sampler's latents) to DIR/*.npy")
     ap.add_argument("--workload", choices=["infer", "stage1", "stage4", "vae", "pipeline"], default="infer",
                     help="infer = cfg-2 next-clip denoise (default, BASELINE metric part 1); "
                          "stage1 = cfg-3 stage-1 pre-training step, bs 2/GPU, data-parallel (metric part 2)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "infer":
+        ap.error("--dump-outputs is implemented for the infer workload only")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -512,7 +522,6 @@ def main():
     imgs = [torch.zeros(3, hw[0] * 8, hw[1] * 8) for _ in range(C)]
     batch = proc.prompt_condition_frame_block_inference([prompt, prompt_], [imgs, []], height=hw[0] * 8, width=hw[1] * 8,
                                                         use_img_cfg=True, frame_blocks=[C, G])
-    dense_mask = batch["attention_mask"].to_bool_tensor()   # only to count the visible pairs (algorithmic FLOPs)
     g = torch.Generator("cpu").manual_seed(42 + rank)
     noise = [torch.randn(1, 4, *hw, generator=g) for _ in range(G)]
     z = [n.to(device, BF) for n in noise] * 2
@@ -529,26 +538,26 @@ def main():
     valid = batch["input_ids"] != 2
     real_tokens = int(valid.sum())
     H, I, nl = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
-    pairs = visible_pairs(dense_mask, valid)
     reuse = eng.S > 0
-    if reuse:
-        # condition prefix computed once per clip (timed: one prefill per timed region): per-step algorithmic work
-        # is the reduced count of SURVEY.md §8d (34.11 TF at cfg-2), the prefill (7.6 TF) is added to the total
-        static_tok = C * (N + 2)
+    # condition prefix computed once per clip (timed: one prefill per timed region): per-step algorithmic work
+    # is the reduced count of SURVEY.md §8d (34.11 TF at cfg-2), the prefill (7.6 TF) is added to the total
+    static_tok = C * (N + 2) if reuse else 0
+    real_tokens_step = real_tokens - static_tok
+    if args.full:
+        dense_mask = batch["attention_mask"].to_bool_tensor()   # only to count the visible pairs (algorithmic FLOPs)
+        pairs = visible_pairs(dense_mask, valid)
         pairs_static = int(dense_mask[0, :static_tok].sum().item())
-        real_tokens_step, pairs_step = real_tokens - static_tok, pairs - pairs_static
-    else:
-        real_tokens_step, pairs_step = real_tokens, pairs
-    flops_linear = 2 * (4 * H * H + 3 * H * I) * real_tokens_step * nl
-    flops_attn = 4 * H * pairs_step * nl
-    flops_step = flops_linear + flops_attn
-    # the prefill runs the condition rows only (they never see a later row)
-    flops_prefill = (2 * (4 * H * H + 3 * H * I) * static_tok + 4 * H * pairs_static) * nl if reuse else 0
+        pairs_step = pairs - pairs_static
+        flops_linear = 2 * (4 * H * H + 3 * H * I) * real_tokens_step * nl
+        flops_attn = 4 * H * pairs_step * nl
+        flops_step = flops_linear + flops_attn
+        # the prefill runs the condition rows only (they never see a later row)
+        flops_prefill = (2 * (4 * H * H + 3 * H * I) * static_tok + 4 * H * pairs_static) * nl if reuse else 0
 
     stream = torch.cuda.Stream(device=device)
     use_graph = not args.no_graph
     calibration = None
-    if rank == 0 and not args.no_calibration:
+    if rank == 0 and args.full and not args.no_calibration:
         calibration = [calibrate(device, stream, ops, "before the timed region")]
     with torch.cuda.stream(stream):
         eng.set_latents(torch.cat(z, dim=0))
@@ -562,19 +571,27 @@ def main():
             eng.steps_taken = args.warmup
             eng.run(args.steps, use_graph=use_graph)
         elapsed = D.timed_region(timed, torch.cuda.synchronize, device)
-        # the per-clip passes alone, once more (reported beside the timed number, never subtracted from it): with
-        # --steps other than the scheduler's 50 their share of a step differs from a real clip's
-        setup_s = 0.0
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        eng.per_clip_setup()
-        torch.cuda.synchronize()
-        setup_s = time.perf_counter() - t0
+        # what the timed path returned (StaticDenoiser.run -> the sampler's fp32 latents), copied before any later leg
+        # touches the engine's buffers
+        outputs = {"latents": eng.z.float().cpu().numpy()} if args.dump_outputs and rank == 0 else None
+        if args.full:
+            # the per-clip passes alone, once more (reported beside the timed number, never subtracted from it): with
+            # --steps other than the scheduler's 50 their share of a step differs from a real clip's
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.per_clip_setup()
+            torch.cuda.synchronize()
+            setup_s = time.perf_counter() - t0
     if calibration is not None:
         calibration.append(calibrate(device, stream, ops, "right after the timed region"))
     ms_per_step = elapsed / max(args.steps, 1) * 1e3
     value = world * G * N * args.steps / elapsed
-    finite = bool(torch.isfinite(eng.z).all().item())
+    if outputs is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+    finite = bool(torch.isfinite(eng.z).all().item()) if args.full else None
 
     # ---- roofline: every hot kernel of the step timed live, back to back over the 32 layers on the step's own buffers and
     #      weights (so weights stream from HBM as in the step), one HIP-event pair per kernel KIND on the stream the
@@ -583,7 +600,7 @@ def main():
     #      time (gate_up and qkv + RoPE; o_proj / down_proj too when the vendor library is off); `kernels` lists every GEMM of
     #      the layer with the implementation that served it, and the attention forward. ----
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         nq_, nk_, hd_ = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         rows = eng.Ma if reuse else real_tokens_step
         with torch.cuda.stream(stream):
@@ -806,7 +823,7 @@ def main():
     #      2 warm-up + --stage1-steps (default 10) timed steps on the same model; reported inside the same JSON line ----
     hoisted, rows_per_step = bool(eng.hoist), int(eng.Ma) if reuse else real_tokens_step
     stage1 = None
-    if not args.no_stage1 and args.layers == 32:
+    if args.full and not args.no_stage1 and args.layers == 32:
         del eng
         torch.cuda.empty_cache()
         try:
@@ -819,7 +836,7 @@ def main():
             stage1 = {"error": repr(e)[:300]}
     # ---- the round's other stage (LVM/pipeline.py:558-590): VAE decode / encode per 256^2 frame, 5 steps of 8 frames ----
     vae_obj = None
-    if not args.no_vae:
+    if args.full and not args.no_vae:
         try:
             vae_obj = measure_vae(5, 2, device, D, args.vae_precision, world=world)
         except Exception as e:
@@ -841,13 +858,15 @@ def main():
                                             "warmup + steps steps: an over-count of about 0.25 %",
                            "tokens_computed_per_step": rows_per_step,
                            "tokens_counted_per_step": real_tokens_step,
-                           "per_clip_setup_ms": round(setup_s * 1e3, 2),
-                           "ms_per_step_of_a_50_step_clip": round(((elapsed - setup_s) / max(args.steps, 1) * 50 + setup_s) / 50 * 1e3, 3),
-                           "finite": finite},
+                           "full": args.full},
                 "roofline": roof, "calibration": calibration, "stage1_train": stage1, "vae": vae_obj}
+        if args.full:
+            line["config"].update({"per_clip_setup_ms": round(setup_s * 1e3, 2),
+                                   "ms_per_step_of_a_50_step_clip": round(((elapsed - setup_s) / max(args.steps, 1) * 50 + setup_s) / 50 * 1e3, 3),
+                                   "finite": finite})
         if breakdown:
             line["breakdown_ms_per_step"] = breakdown
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(cfg, dict(batch, attention_mask=dense_mask), with_vae=args.cpu_baseline_vae)
         print(json.dumps(tag_rehearsal(line, args)), flush=True)
     if world > 1:

@@ -1,5 +1,5 @@
 set -o pipefail
-B="--steps 30 --warmup 5 --no-stage1 --no-vae --no-cpu-baseline"
+B="--steps 30 --warmup 5 --full --no-stage1 --no-vae --no-cpu-baseline"
 for i in 1 2; do
 for p in 1 0; do
 VGPT_ATTN_P2=$p timeout -k 10 200 python bench.py $B > gpurun_out/r04_ab_attn_p2_${p}_$i.json.log 2> gpurun_out/ab.err || exit 1

@@ -4,7 +4,7 @@ waves' cycles go.
 usage (on the GPU box, after
   rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY
             SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_VALU_MFMA_MOPS_BF16 -d gpurun_out/pmc_sq -o p --output-format csv
-            -- python3 bench.py --steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-stage1
+            -- python3 bench.py --steps 2 --warmup 1 --full --no-graph --no-cpu-baseline --no-stage1
 ):  python scripts/pmc_mfma.py gpurun_out/pmc_sq profiles/r01_pmc_mfma.json
 mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (4 * SQ_BUSY_CU_CYCLES): the counter adds the busy cycles of the matrix
 pipes of all SIMDs (MI355X_MICROARCH.md: = 32 x N_mfma for 32x32x16 bf16), SQ_BUSY_CU_CYCLES the cycles a CU had a wave,

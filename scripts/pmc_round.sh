@@ -5,7 +5,7 @@
 set -o pipefail
 TAG=$1; shift
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
-B="--steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-stage1 --no-vae --no-calibration $*"
+B="--steps 2 --warmup 1 --full --no-graph --no-cpu-baseline --no-stage1 --no-vae --no-calibration $*"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 280 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_VALU_MFMA_MOPS_BF16 -d $ROOT/gpurun_out/${TAG}_pmc_sq -o p --output-format csv -- python3 $ROOT/bench.py $B > $ROOT/gpurun_out/${TAG}_pmc_sq.log 2>&1 || exit 1
 timeout -k 10 280 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $ROOT/gpurun_out/${TAG}_pmc_fetch -o p --output-format csv -- python3 $ROOT/bench.py $B > $ROOT/gpurun_out/${TAG}_pmc_fetch.log 2>&1 || exit 1

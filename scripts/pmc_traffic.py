@@ -2,9 +2,9 @@
 profiles/<name>.json: per-kernel average beyond-L2 traffic per launch.
 
 usage (on the GPU box, after
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o p --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-stage1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmc_write -o p --output-format csv -- python3 bench.py ... (same)
-):  python scripts/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/r01_pmc_traffic_v2.json
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d pmc_fetch -o p --output-format csv -- python3 bench.py --steps 2 --warmup 1 --full --no-graph --no-cpu-baseline --no-stage1
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d pmc_write -o p --output-format csv -- python3 bench.py ... (same)
+):  python scripts/pmc_traffic.py pmc_fetch pmc_write profiles/r01_pmc_traffic_v2.json
 traffic_bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024: FETCH_SIZE counts 128-byte requests of wide coalesced reads as 64 B
 on gfx950; both counters sit on the fabric side of the L2, so Infinity-Cache hits are included (upper bound on HBM)."""
 import collections, csv, glob, json, sys

@@ -80,3 +80,58 @@ def sampled_grad(gr: torch.Tensor, cap: int = 6000) -> np.ndarray:
 
 def load(name):
     return np.load(os.path.join(GOLD, name))
+
+
+def save_values(path, values: dict):
+    """Store a dict of tensors, lists of tensors and plain Python values (ints, lists, tuples, dicts, None) as one .npz:
+    tensors keep their dtype, plain values are stored as their repr and come back through ast.literal_eval, so a loaded
+    value compares with == / torch.equal exactly as the original object did (tuples stay tuples, int keys stay ints)."""
+    out = {}
+    for k, v in values.items():
+        if torch.is_tensor(v):
+            out[f"t__{k}"] = v.numpy()
+        elif isinstance(v, list) and v and all(torch.is_tensor(x) for x in v):
+            out[f"n__{k}"] = np.asarray(len(v))
+            for i, x in enumerate(v):
+                out[f"l__{k}__{i}"] = x.numpy()
+        else:
+            out[f"r__{k}"] = np.asarray(repr(v))
+    np.savez_compressed(path, **out)
+
+
+def load_values(name) -> dict:
+    """Inverse of save_values for tests/golden/<name>."""
+    import ast
+    d = np.load(os.path.join(GOLD, name))
+    out = {}
+    for key in d.files:
+        kind, k = key.split("__", 1)
+        if kind == "t":
+            out[k] = torch.from_numpy(d[key])
+        elif kind == "n":
+            out[k] = [torch.from_numpy(d[f"l__{k}__{i}"]) for i in range(int(d[key]))]
+        elif kind == "r":
+            out[k] = ast.literal_eval(str(d[key]))
+    return out
+
+
+def train_collator_features(processor_cls, SpecialTokenizer):
+    """Features for TrainDataCollator (stage-1 layout, F = 3) and TrainDataCollator_FrameBlock (frame blocks [1, 2, 1]) as
+    the processor lays them out (tests/test_dropin_imports.py; their reference-collated form is
+    tests/golden/ref_train_collators.npz)."""
+    proc = processor_cls(SpecialTokenizer(10, 11, 12))
+    F = 3
+    prompt = "".join(f"<|diffusion|><|image_{i + 1}|><img><|image_{i + 1}|></img>" if i < F - 1 else f"<|diffusion|><|image_{i + 1}|>"
+                     for i in range(F))
+    feat = proc.process_multi_modal_prompt_training(prompt, [torch.full((3, 64, 64), float(i)) for i in range(F)])
+    fbs = [1, 2, 1]
+    prompt2, i, j, n = "", 0, 0, 0
+    for k, fb in enumerate(fbs):
+        for _ in range(fb):
+            prompt2 += f"<|diffusion|><|image_{i + 1}|>"; i += 1; n += 1
+        if k != len(fbs) - 1:
+            for _ in range(fb):
+                prompt2 += f"<img><|image_{j + 1}|></img>"; j += 1
+    feat2 = proc.process_multi_modal_prompt_frame_block_training(prompt2, [torch.full((3, 64, 64), float(q)) for q in range(n)], fbs)
+    feat2["frame_blocks"] = fbs
+    return feat, F, feat2, fbs, len(feat2["image_sizes"])

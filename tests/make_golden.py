@@ -80,6 +80,39 @@ def collator_vectors():
         np.savez_compressed(os.path.join(OUT, f"ref_collator_call_I{n_img}s{side}o{hw[0]}x{hw[1]}cfg{int(cfg_on)}sp{sp}{via}.npz"), **d)
 
 
+def live_collator_vectors():
+    """The reference collator's whole output where the tests compare objects, not only ids / masks / sizes: the
+    next-clip requests of test_collator.py::test_live_reference_inference, create_mask / create_position with targets of
+    different sizes, and TrainDataCollator / TrainDataCollator_FrameBlock (LVM/train_helper/data.py:404-537) on the
+    processor's features (test_dropin_imports.py)."""
+    import copy
+    import importlib
+    from tests import glue_cases as GC
+    for C, G, N, sp in [(3, 1, 4, 1), (1, 1, 16, 8), (5, 4, 9, 2)]:
+        b = X.reference_inference_batch(C, G, N, sp=sp)
+        GC.save_values(os.path.join(OUT, f"ref_collator_live_C{C}G{G}N{N}sp{sp}.npz"),
+                       {k: b[k] for k in ("input_ids", "position_ids", "attention_mask", "input_image_sizes",
+                                          "denoise_image_sizes", "time_emb_inx", "frame_blocks")})
+    ns = X.collator_classes()
+    coll = ns.LVMCollator(pad_token_id=2, hidden_size=8)
+    valid = torch.ByteTensor([[1, 1, 1, 1], [0, 0, 1, 1]])
+    rm, rp = coll.create_mask(valid, [16, 8])
+    GC.save_values(os.path.join(OUT, "ref_collator_short_target.npz"),
+                   dict(mask=rm, position=coll.create_position(valid, [16, 8]),
+                        pad_shapes=[None if q is None else tuple(q.shape) for q in rp]))
+    P = importlib.import_module("video-gpt_amd.processor")
+    feat, F, feat2, fbs, n_slots = GC.train_collator_features(P.LVMProcessor, P.SpecialTokenizer)
+    data = X._extract("LVM/train_helper/data.py", ["TrainDataCollator", "TrainDataCollator_FrameBlock"],
+                      extra_ns={"LVMCollator": ns.LVMCollator, "copy": copy})
+    out = {}
+    for tag, b in (("stage1_", data.TrainDataCollator(2, 8, True, F, batch_size=2)([copy.deepcopy(feat)])),
+                   ("frame_block_", data.TrainDataCollator_FrameBlock(2, 8, True, n_slots, batch_size=1)([copy.deepcopy(feat2)]))):
+        for k in ("input_ids", "position_ids", "attention_mask", "input_image_sizes", "denoise_image_sizes", "time_emb_inx",
+                  "input_pixel_values", "output_images"):
+            out[tag + k] = b[k]
+    GC.save_values(os.path.join(OUT, "ref_train_collators.npz"), out)
+
+
 def scheduler_vectors():
     Sched = X.scheduler_class()
     out = {}
@@ -379,6 +412,7 @@ if __name__ == "__main__":
         raise SystemExit("reference checkout not found: golden vectors can only be regenerated in the build container")
     os.makedirs(OUT, exist_ok=True)
     collator_vectors()
+    live_collator_vectors()
     scheduler_vectors()
     leaf_vectors()
     lvm_glue_vectors()

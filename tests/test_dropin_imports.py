@@ -95,46 +95,28 @@ def test_parallel_states_single_process(dropin, monkeypatch):
 
 def test_train_collators_match_reference_index_conventions(dropin):
     """TrainDataCollator / TrainDataCollator_FrameBlock (LVM/train_helper/data.py:404-537) on features laid out by the
-    processor; live against the reference's own classes when its checkout is present."""
+    processor, against the reference's own classes' output on the same features (tests/golden/ref_train_collators.npz,
+    tests/make_golden.py)."""
     from LVM import LVMProcessor
     from LVM.train_helper import TrainDataCollator, TrainDataCollator_FrameBlock
+    from tests import glue_cases as GC
     P = importlib.import_module("video-gpt_amd.processor")
-    proc = LVMProcessor(P.SpecialTokenizer(10, 11, 12))
-    F = 3
-    prompt = "".join(f"<|diffusion|><|image_{i + 1}|><img><|image_{i + 1}|></img>" if i < F - 1 else f"<|diffusion|><|image_{i + 1}|>"
-                     for i in range(F))
-    feat = proc.process_multi_modal_prompt_training(prompt, [torch.full((3, 64, 64), float(i)) for i in range(F)])
+    feat, F, feat2, fbs, n_slots = GC.train_collator_features(LVMProcessor, P.SpecialTokenizer)
     out = TrainDataCollator(2, 8, True, F, batch_size=2)([feat])
     assert out["input_ids"].shape[0] == 2                              # the lone sample is repeated to the batch size
     assert len(out["output_images"]) == 2 * F and len(out["input_pixel_values"]) == 2 * (F - 1)
     assert out["time_emb_inx"][0] == [s[0] - 1 for s in out["denoise_image_sizes"][0]]
-    fbs = [1, 2, 1]
-    prompt2, i, j, n = "", 0, 0, 0
-    for k, fb in enumerate(fbs):
-        for _ in range(fb):
-            prompt2 += f"<|diffusion|><|image_{i + 1}|>"; i += 1; n += 1
-        if k != len(fbs) - 1:
-            for _ in range(fb):
-                prompt2 += f"<img><|image_{j + 1}|></img>"; j += 1
-    feat2 = proc.process_multi_modal_prompt_frame_block_training(prompt2, [torch.full((3, 64, 64), float(q)) for q in range(n)], fbs)
-    feat2["frame_blocks"] = fbs
-    n_slots = len(feat2["image_sizes"])
     out2 = TrainDataCollator_FrameBlock(2, 8, True, n_slots, batch_size=1)([feat2])
     assert len(out2["denoise_image_sizes"][0]) == sum(fbs) and len(out2["input_image_sizes"][0]) == sum(fbs[:-1])
-    from oracle import extract_reference as X
-    if X.available():
-        import copy
-        ns = X.collator_classes()
-        data = X._extract("LVM/train_helper/data.py", ["TrainDataCollator", "TrainDataCollator_FrameBlock"],
-                          extra_ns={"LVMCollator": ns.LVMCollator, "copy": copy})
-        ref = data.TrainDataCollator(2, 8, True, F, batch_size=2)([copy.deepcopy(feat)])
-        ref2 = data.TrainDataCollator_FrameBlock(2, 8, True, n_slots, batch_size=1)([copy.deepcopy(feat2)])
-        for a, b in ((out, ref), (out2, ref2)):
-            for k in ("input_ids", "position_ids"):
-                assert torch.equal(a[k], b[k])
-            assert torch.equal(a["attention_mask"].bool(), b["attention_mask"].bool())
-            for k in ("input_image_sizes", "denoise_image_sizes", "time_emb_inx"):
-                assert {kk: [list(x) if isinstance(x, (list, tuple)) else x for x in v] for kk, v in a[k].items()} == \
-                       {kk: [list(x) if isinstance(x, (list, tuple)) else x for x in v] for kk, v in b[k].items()}
-            for k in ("input_pixel_values", "output_images"):
-                assert len(a[k]) == len(b[k]) and all(torch.equal(u, v) for u, v in zip(a[k], b[k]))
+    gold = GC.load_values("ref_train_collators.npz")
+    ref = {k[len("stage1_"):]: v for k, v in gold.items() if k.startswith("stage1_")}
+    ref2 = {k[len("frame_block_"):]: v for k, v in gold.items() if k.startswith("frame_block_")}
+    for a, b in ((out, ref), (out2, ref2)):
+        for k in ("input_ids", "position_ids"):
+            assert torch.equal(a[k], b[k])
+        assert torch.equal(a["attention_mask"].bool(), b["attention_mask"].bool())
+        for k in ("input_image_sizes", "denoise_image_sizes", "time_emb_inx"):
+            assert {kk: [list(x) if isinstance(x, (list, tuple)) else x for x in v] for kk, v in a[k].items()} == \
+                   {kk: [list(x) if isinstance(x, (list, tuple)) else x for x in v] for kk, v in b[k].items()}
+        for k in ("input_pixel_values", "output_images"):
+            assert len(a[k]) == len(b[k]) and all(torch.equal(u, v) for u, v in zip(a[k], b[k]))
