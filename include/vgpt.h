@@ -254,6 +254,42 @@ int vgpt_attn_fwd_plan_fp8(const void* workspace, void* o, const uint32_t* bits,
                            const uint16_t* item_summary, const int32_t* order, int64_t n_items, int64_t B, int64_t L,
                            int n_heads, int n_kv_heads, int head_dim, int64_t o_sb, int64_t o_sh, int64_t o_ss, void* stream);
 
+/* ---- MX-fp8 projections (inference option `linear_precision = "fp8"` of the sampler's per-step forward: qkv_proj, o_proj,
+ * gate_up_proj, down_proj of every decoder layer).  Number format as the MX-fp8 attention: OCP e4m3 in blocks of 32
+ * consecutive k of a row sharing an E8M0 scale 2^e, e the smallest exponent with amax 2^-e <= 448 (clamped to [-127, 127]),
+ * elements rounded to nearest-even, an all-zero block stored as zero payload (scale byte 127).
+ *
+ * Record of a (rows, K) matrix, vgpt_mx8_bytes(rows, K) bytes (-1: K not a positive multiple of 32), 256-byte aligned:
+ *   payload  at 0: MG = ceil(rows / 32) row groups x KB = ceil(K / 64) k tiles of 2048 bytes; byte
+ *            ((g * KB + kb) * 2 + p) * 1024 + l * 16 + j  holds element (row 32 g + (l & 31), k 64 kb + 32 p + 16 (l >> 5) + j)
+ *            for l in [0, 64), j in [0, 16) -- the operand fragment of lane l of the block-scaled 32x32x64 MFMA;
+ *   scales   at align256(MG * KB * 2048): byte (g * KB + kb) * 64 + l = E8M0 exponent + 127 of row 32 g + (l & 31),
+ *            k block [64 kb + 32 (l >> 5), +32).
+ * Rows >= rows and k >= K (padding up to the group / tile) hold zero payload and scale byte 127.
+ *   vgpt_mx8_quant_rows: x (rows, K) bf16, row stride ldx -> record `out`; rstd_out (nullable): rsqrt(mean_k x^2 + eps) of
+ *       every row in fp32 (the RMSNorm statistic, as vgpt_rms_rstd) -- the activations in front of a projection;
+ *   vgpt_mx8_quant_weight: W (N, K) bf16 row-major, times gain (K) bf16 per column when gain != NULL (multiplied in fp32,
+ *       rounded once to e4m3: the RMSNorm gain folded into the weight) -> record `out`;
+ *   vgpt_gemm_mx8: C (M, .) bf16 from the records A8 (M, K) and W8 (N, K), fp32 accumulation in a fixed k order per output
+ *       element (no split-K, no atomics: a row's result does not depend on M or on the tile that computed it), epilogue
+ *         VGPT_MX8_EPI_NONE   C = A W^T;
+ *         VGPT_MX8_EPI_RESID  C = A W^T + resid (row stride ldr; C may be resid) -- vgpt_gemm_bf16 with VGPT_EPI_RESID;
+ *         VGPT_MX8_EPI_ROPE   row m of A W^T times rstd[m], rounded to bf16, then columns [0, n_rot_heads * head_dim) rotated
+ *                             with cos / sin (M, head_dim / 2) fp32 -- vgpt_gemm_bf16_rope_prenorm; head_dim 96, N % 96 == 0;
+ *         VGPT_MX8_EPI_GATED  W8 = [Wg ; Wu] (N = 2 I rows): C (M, I) = act(gate) * up with gate / up = row m of the product
+ *                             times rstd[m], rounded to bf16 -- vgpt_gated_mlp_act_fwd_prenorm; I % 32 == 0.
+ *       K % 32 == 0, N % 32 == 0, ldc % 4 == 0; arguments are checked before any launch. */
+#define VGPT_MX8_EPI_NONE 0
+#define VGPT_MX8_EPI_RESID 1
+#define VGPT_MX8_EPI_ROPE 2
+#define VGPT_MX8_EPI_GATED 3
+int64_t vgpt_mx8_bytes(int64_t rows, int64_t K);
+int vgpt_mx8_quant_rows(const void* x, int64_t ldx, void* out, float* rstd_out, int64_t rows, int64_t K, float eps, void* stream);
+int vgpt_mx8_quant_weight(const void* W, const void* gain, void* out, int64_t N, int64_t K, void* stream);
+int vgpt_gemm_mx8(const void* A8, const void* W8, void* C, const void* resid, const float* rstd, const float* cos_t,
+                  const float* sin_t, int64_t M, int64_t N, int64_t K, int64_t ldc, int64_t ldr, int epilogue, int n_rot_heads,
+                  int head_dim, int act, void* stream);
+
 /* order (B, ceil(L/128) - q_start/128) int32 <- the 128-row q blocks [q_start/128, ...) of every batch item, the one
  * with the most non-empty 64-key tiles first (stable). */
 int vgpt_attn_qblock_order(const uint8_t* summary, int64_t B, int64_t L, int64_t q_start, int32_t* order, void* stream);

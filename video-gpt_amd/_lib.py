@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("VGPT_LIB") or os.path.join(_HERE, "libvgpt_hip.so")
 # enums mirrored from include/vgpt.h
 ACT_SILU, ACT_GELU, ACT_GELU_TANH, ACT_NONE = 0, 1, 2, 3
 EPI_NONE, EPI_RESID, EPI_BIAS = 0, 1, 2
+MX8_EPI_NONE, MX8_EPI_RESID, MX8_EPI_ROPE, MX8_EPI_GATED = 0, 1, 2, 3
 PRED_V, PRED_X1 = 0, 1
 
 _P = c_void_p
@@ -65,6 +66,10 @@ SIGNATURES = {
     "vgpt_attn_fp8_workspace_bytes": (_I64, [_I64, _I64, c_int, c_int, c_int]),
     "vgpt_attn_fp8_quantize": (c_int, [_P] * 4 + [_I64, _I64, _I64, c_int, c_int, c_int] + [_I64] * 9 + [c_float, _P]),
     "vgpt_attn_fwd_plan_fp8": (c_int, [_P] * 6 + [_I64, _I64, _I64, c_int, c_int, c_int] + [_I64] * 3 + [_P]),
+    "vgpt_mx8_bytes": (_I64, [_I64, _I64]),
+    "vgpt_mx8_quant_rows": (c_int, [_P, _I64, _P, _P, _I64, _I64, c_float, _P]),
+    "vgpt_mx8_quant_weight": (c_int, [_P, _P, _P, _I64, _I64, _P]),
+    "vgpt_gemm_mx8": (c_int, [_P] * 7 + [_I64] * 5 + [c_int, c_int, c_int, c_int, _P]),
     "vgpt_embed_gather": (c_int, [_P, _P, _P, _I64, _I64, _I64, _P]),
     "vgpt_patch_embed_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _I64, c_int, _P]),
     "vgpt_timestep_sinusoid": (c_int, [_P, _P, _P, c_int, c_int, _P]),

@@ -100,7 +100,7 @@ class StaticDenoiser:
                  denoise_image_sizes, time_emb_inx, n_frames: int, latent_hw, use_img_cfg: bool, img_cfg_scale: float,
                  prediction_type: str = "v", sigma: Optional[torch.Tensor] = None, pack_padding: bool = True,
                  reuse_condition_prefix: bool = False, hoist_special_rows: bool = True,
-                 attention_precision: str = "bf16", fuse_norms: Optional[bool] = None):
+                 attention_precision: str = "bf16", fuse_norms: Optional[bool] = None, linear_precision: str = "bf16"):
         model._check_ready()
         # fuse_norms: the two RMSNorms of a decoder layer folded into the GEMMs around them in the per-step forward (ops:
         # linear_resid_ssq -> *_prenorm; include/vgpt.h).  None = on wherever the step's shapes allow it, VGPT_FUSE_NORMS=0
@@ -110,6 +110,12 @@ class StaticDenoiser:
         # "fp8": the per-step attention of the sampler runs on MX-fp8 operands (csrc/attn_fp8.hip; the cfg-5 option of
         # SURVEY.md §8d).  The per-clip passes (prefill, time rows) stay bf16.
         self.attn_fp8 = attention_precision == "fp8"
+        if linear_precision not in ("bf16", "fp8"):
+            raise VgptError(f"StaticDenoiser: linear_precision must be 'bf16' or 'fp8' (got {linear_precision!r})")
+        # "fp8": the four projections of every decoder layer in the per-step forward run as MX-fp8 GEMMs (csrc/gemm_mx8.hip) on
+        # activations quantised per step and weights quantised from the live parameters once per clip (per_clip_setup).  The
+        # per-clip passes, embeddings, final norm and final layer stay bf16.
+        self.lin_fp8 = linear_precision == "fp8"
         # query rows per work item of the per-step bf16 attention: 128 = the four-wave kernel, two workgroups per CU (product).
         # 256 = the eight-wave kernel (one K / V tile staged per 256 rows: half the LDS-DMA instructions per wave and half the
         # L2 -> LDS bytes per FLOP; head dim 96): bit-identical results, measured SLOWER in round 3 -- 159.5 / 160.4 us per
@@ -282,7 +288,19 @@ class StaticDenoiser:
         self.fuse = None
         if fuse_norms is None:
             fuse_norms = os.environ.get("VGPT_FUSE_NORMS", "1") != "0"
-        if fuse_norms:
+        self.mx8 = None
+        if self.lin_fp8:
+            # the fp8 step folds both RMSNorms itself (row quantiser -> rstd, gain in the quantised weight): no folded bf16
+            # copies.  Records at stable addresses (a captured graph reads them), weights refilled by every per_clip_setup()
+            Ms = self.Ma if S else B * L
+            W3 = (nq + 2 * nk) * hd
+            mk = lambda rows, K: ops.Mx8Tensor(rows, K, dev)
+            self.mx8 = {"a_hid": mk(Ms, H), "a_ctx": mk(Ms, nq * hd), "a_act": mk(Ms, I),
+                        "rstd": torch.empty(Ms, dtype=torch.float32, device=dev),
+                        "w": [{"qkv": mk(W3, H), "o": mk(H, nq * hd), "gate_up": mk(2 * I, H), "down": mk(H, I)}
+                              for _ in model.llm.layers]}
+            self.quantize_weights()
+        elif fuse_norms:
             Ms = self.Ma if S else B * L
             wa, wb = ops.norm_workspace_bytes(Ms, H, nq * hd), ops.norm_workspace_bytes(Ms, H, I)
             if wa > 0 and wb > 0:
@@ -359,15 +377,29 @@ class StaticDenoiser:
         return self
 
     def per_clip_setup(self):
-        """Everything a clip computes once instead of once per step: the condition prefix and the special rows of every step
-        (one pass, _clip_pass; prefill() alone when the layout cannot be hoisted), the final layer's adaLN modulation of
-        every step."""
+        """Everything a clip computes once instead of once per step: the MX-fp8 weights (linear_precision "fp8"), the
+        condition prefix and the special rows of every step (one pass, _clip_pass; prefill() alone when the layout cannot be
+        hoisted), the final layer's adaLN modulation of every step."""
+        self.quantize_weights()
         if self.S:
             if self.hoist:
                 self._clip_pass()
             else:
                 self.prefill()
         self._mod_pass()
+
+    def quantize_weights(self):
+        """linear_precision "fp8": every decoder layer's qkv / o / gate_up / down weights into their MX-fp8 records, from the
+        LIVE parameters (and, for qkv and gate_up, the live RMSNorm gains folded in), so a sampler call never runs weights older
+        than the call.  No-op otherwise."""
+        if self.mx8 is None:
+            return
+        for layer, w in zip(self.model.llm.layers, self.mx8["w"]):
+            at, mlp = layer.self_attn, layer.mlp
+            ops.mx8_quantize_weight(at.qkv_proj.weight, layer.input_layernorm.weight, out=w["qkv"])
+            ops.mx8_quantize_weight(at.o_proj.weight, out=w["o"])
+            ops.mx8_quantize_weight(mlp.gate_up_proj.weight, layer.post_attention_layernorm.weight, out=w["gate_up"])
+            ops.mx8_quantize_weight(mlp.down_proj.weight, out=w["down"])
 
     def set_sigma(self, sigma: torch.Tensor):
         self.sigma = sigma.to(self.dev, torch.float32).contiguous()
@@ -541,14 +573,20 @@ class StaticDenoiser:
             # written by linear_resid_ssq, which leaves the next norm's partial sums of squares behind
             ops.rms_rstd(self.hid, m.llm.layers[0].input_layernorm.variance_epsilon, out=fz["rstd_in"])
 
+        mx = self.mx8
+
         def qkv_proj(li_, layer, out):
             at = layer.self_attn
+            if mx is not None:
+                ops.mx8_quantize_rows(self.hid, mx["a_hid"], mx["rstd"], layer.input_layernorm.variance_epsilon)
+                return ops.linear_mx8(mx["a_hid"], mx["w"][li_]["qkv"], out, "rope", rstd=mx["rstd"], cos=rope[0], sin=rope[1],
+                                      n_rot_heads=nq + nk, head_dim=hd)
             if fz is None:
                 return ops.linear_qkv_rope(self.nrm, at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=out)
             return ops.linear_qkv_rope_prenorm(self.hid, fz["wq"][li_], rope[0], rope[1], fz["rstd_in"], nq, nk, hd, out=out)
         for li_, layer in enumerate(m.llm.layers):
             at, mlp = layer.self_attn, layer.mlp
-            if fz is None:
+            if fz is None and mx is None:
                 ops.rmsnorm(self.hid, layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=self.nrm)
             if S:
                 full = self.qkv_full[li_]
@@ -570,6 +608,15 @@ class StaticDenoiser:
                                             item_rows=self.attn_item_rows)
                 else:
                     ops.attention_qkv(self.qkv, self.pm, nq, nk, hd, out=self.ctx)
+            if mx is not None:
+                w = mx["w"][li_]
+                ops.mx8_quantize_rows(self.ctx, mx["a_ctx"])
+                ops.linear_mx8(mx["a_ctx"], w["o"], self.hid, "resid", residual=self.hid)
+                ops.mx8_quantize_rows(self.hid, mx["a_hid"], mx["rstd"], layer.post_attention_layernorm.variance_epsilon)
+                ops.linear_mx8(mx["a_hid"], w["gate_up"], self.act, "gated", rstd=mx["rstd"], act=mlp.act)
+                ops.mx8_quantize_rows(self.act, mx["a_act"])
+                ops.linear_mx8(mx["a_act"], w["down"], self.hid, "resid", residual=self.hid)
+                continue
             if fz is not None:
                 ops.linear_resid_rstd(self.ctx, at.o_proj.weight, self.hid, fz["rstd_post"], fz["ws"],
                                       layer.post_attention_layernorm.variance_epsilon, out=self.hid)

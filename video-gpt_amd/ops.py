@@ -265,6 +265,94 @@ def gated_mlp_act(x: torch.Tensor, w_gate_up: torch.Tensor, act: int = ACT_SILU,
     return out
 
 
+# ---- MX-fp8 projections (include/vgpt.h: vgpt_mx8_* / vgpt_gemm_mx8; the sampler's linear_precision = "fp8") ----
+
+class Mx8Tensor:
+    """A (rows, K) matrix in the MX-fp8 record layout of include/vgpt.h (e4m3 payload + E8M0 scales) in one uint8 buffer."""
+
+    def __init__(self, rows: int, K: int, device):
+        nbytes = int(_lib.load().vgpt_mx8_bytes(rows, K))
+        if nbytes < 0:
+            raise VgptError(f"mx8: K must be a positive multiple of 32 (got rows {rows}, K {K})")
+        self.rows, self.K = int(rows), int(K)
+        self.data = torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    def data_ptr(self) -> int:
+        return self.data.data_ptr()
+
+
+def mx8_quantize_rows(x: torch.Tensor, out: Mx8Tensor, rstd: Optional[torch.Tensor] = None, eps: float = 1e-6) -> Mx8Tensor:
+    """x (..., K) bf16 -> `out`; rstd (M,) fp32 (optional): the rows' RMSNorm statistic rsqrt(mean(x^2) + eps)."""
+    _chk(x, BF16, "mx8_quantize_rows.x")
+    K = x.shape[-1]
+    M = x.numel() // K
+    if (out.rows, out.K) != (M, K):
+        raise VgptError(f"mx8_quantize_rows: record holds ({out.rows}, {out.K}), x is ({M}, {K})")
+    if rstd is not None:
+        _chk(rstd, torch.float32, "mx8_quantize_rows.rstd")
+        if rstd.numel() != M:
+            raise VgptError("mx8_quantize_rows: rstd size mismatch")
+    call("vgpt_mx8_quant_rows", x.data_ptr(), K, out.data_ptr(), _ptr(rstd), M, K, float(eps), _stream())
+    return out
+
+
+def mx8_quantize_weight(weight: torch.Tensor, gain: Optional[torch.Tensor] = None, out: Optional[Mx8Tensor] = None) -> Mx8Tensor:
+    """weight (N, K) bf16 [x gain (K) per column, in fp32] -> MX-fp8 record (the RMSNorm gain folded in when given)."""
+    _chk(weight, BF16, "mx8_quantize_weight.weight")
+    N, K = weight.shape
+    if out is None:
+        out = Mx8Tensor(N, K, weight.device)
+    elif (out.rows, out.K) != (N, K):
+        raise VgptError(f"mx8_quantize_weight: record holds ({out.rows}, {out.K}), weight is ({N}, {K})")
+    if gain is not None:
+        _chk(gain, BF16, "mx8_quantize_weight.gain")
+        if gain.numel() != K:
+            raise VgptError("mx8_quantize_weight: gain size mismatch")
+    call("vgpt_mx8_quant_weight", weight.data_ptr(), _ptr(gain), out.data_ptr(), N, K, _stream())
+    return out
+
+
+_MX8_EPI = {"none": _lib.MX8_EPI_NONE, "resid": _lib.MX8_EPI_RESID, "rope": _lib.MX8_EPI_ROPE, "gated": _lib.MX8_EPI_GATED}
+
+
+def linear_mx8(a: Mx8Tensor, w: Mx8Tensor, out: torch.Tensor, epilogue: str = "none", residual: Optional[torch.Tensor] = None,
+               rstd: Optional[torch.Tensor] = None, cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None,
+               n_rot_heads: int = 0, head_dim: int = 96, act: int = ACT_SILU) -> torch.Tensor:
+    """MX-fp8 GEMM out = a w^T with an epilogue: "none"; "resid" (+ residual, may be `out`: o_proj / down_proj);
+    "rope" (rows times rstd, RoPE on the first n_rot_heads heads: qkv_proj behind a folded RMSNorm); "gated"
+    (w = [Wg ; Wu], out (M, N / 2) = act(gate) * up from rows times rstd: gate_up_proj behind a folded RMSNorm)."""
+    if epilogue not in _MX8_EPI:
+        raise VgptError(f"linear_mx8: unknown epilogue {epilogue!r}")
+    if a.K != w.K:
+        raise VgptError("linear_mx8: K mismatch")
+    M, N, K = a.rows, w.rows, a.K
+    _chk(out, BF16, "linear_mx8.out")
+    n_out = N // 2 if epilogue == "gated" else N
+    if out.numel() != M * n_out:
+        raise VgptError("linear_mx8: out shape mismatch")
+    if epilogue == "resid":
+        if residual is None:
+            raise VgptError("linear_mx8: the resid epilogue needs a residual")
+        _chk(residual, BF16, "linear_mx8.residual")
+        if residual.numel() != M * N:
+            raise VgptError("linear_mx8: residual shape mismatch")
+    if epilogue in ("rope", "gated"):
+        if rstd is None:
+            raise VgptError(f"linear_mx8: the {epilogue} epilogue needs rstd")
+        _chk(rstd, torch.float32, "linear_mx8.rstd")
+        if rstd.numel() != M:
+            raise VgptError("linear_mx8: rstd size mismatch")
+    if epilogue == "rope":
+        if cos is None or sin is None:
+            raise VgptError("linear_mx8: the rope epilogue needs cos / sin")
+        _chk(cos, torch.float32, "linear_mx8.cos"); _chk(sin, torch.float32, "linear_mx8.sin")
+        if cos.numel() != M * (head_dim // 2) or sin.numel() != cos.numel():
+            raise VgptError("linear_mx8: cos / sin table size mismatch")
+    call("vgpt_gemm_mx8", a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(residual), _ptr(rstd), _ptr(cos), _ptr(sin), M, N, K,
+         n_out, N, _MX8_EPI[epilogue], int(n_rot_heads), int(head_dim), int(act), _stream())
+    return out
+
+
 # ---- attention --------------------------------------------------------------------------------
 
 class AttnPlan:

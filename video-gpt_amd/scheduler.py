@@ -36,6 +36,7 @@ class LVMScheduler:
         self.reuse_condition_prefix = True   # compute the step-invariant condition rows once per clip (engine.py)
         self.hoist_special_rows = True       # ... and the <|diffusion|> / time rows of all steps in one pass (needs a TokenLayout mask)
         self.attention_precision = "bf16"    # "fp8": MX-fp8 attention in the sampler steps of the fast path (cfg-5 option)
+        self.linear_precision = "bf16"       # "fp8": MX-fp8 qkv / o / gate_up / down projections in the fast path's steps
         self.fuse_norms = None               # None: RMSNorms folded into the GEMMs wherever the step's shapes allow (engine.py); False: never
         # keep the engine of a clip on the model and re-use it for the next clip of an identical sequence (the rounds of a
         # rollout once the window is full: LVM/pipeline.py:418-422 re-creates the same prompt every round): buffers, attention
@@ -92,7 +93,7 @@ class LVMScheduler:
                 len(z), tuple(z[0].shape), None if not lat else (len(lat), tuple(lat[0].shape)),
                 bool(model_kwargs["use_img_cfg"]), float(model_kwargs["img_cfg_scale"]), prediction_type, tb(self.sigma),
                 self.pack_padding, self.reuse_condition_prefix, self.hoist_special_rows, self.attention_precision,
-                self.fuse_norms, str(z[0].device),
+                self.linear_precision, self.fuse_norms, str(z[0].device),
                 # the captured graph holds the parameters' device addresses: parameters moved or re-allocated since
                 # (model.to(...), a new state dict assigned tensor by tensor) must not meet a cached graph
                 tuple(p_.data_ptr() for p_ in self._owner_params))
@@ -105,7 +106,8 @@ class LVMScheduler:
                               prediction_type, sigma=self.sigma, pack_padding=self.pack_padding,
                               reuse_condition_prefix=self.reuse_condition_prefix,
                               hoist_special_rows=self.hoist_special_rows,
-                              attention_precision=self.attention_precision, fuse_norms=self.fuse_norms)
+                              attention_precision=self.attention_precision, linear_precision=self.linear_precision,
+                              fuse_norms=self.fuse_norms)
 
     def __call__(self, z, func, model_kwargs, use_kv_cache: bool = True, offload_kv_cache: bool = True,
                  prediction_type: str = "v", vae=None, noise_level=None):
@@ -125,6 +127,10 @@ class LVMScheduler:
             frames = mixed
 
         engine = self._fast_path_engine(frames, func, model_kwargs, prediction_type) if is_list else None
+        if engine is None and self.linear_precision != "bf16":
+            # the fp8 projections exist in the engine's per-step forward only: no silent bf16 run of another path
+            raise VgptError(f"LVMScheduler: linear_precision={self.linear_precision!r} needs the fast path (StaticDenoiser: "
+                            "frame_block_forward_with_cfg of this package on a list of equal-shape latents)")
         if engine is not None:
             self.last_engine = engine
             stream = torch.cuda.current_stream()
