@@ -49,7 +49,7 @@ const char* vgpt_last_error(void);
 /* VGPT_ABI_VERSION of the library that was loaded.  Bumped with EVERY change of an exported signature; a binding written
  * for another value must refuse to call (video-gpt_amd/_lib.py does): with shifted arguments a stale library would read a
  * stream pointer as a scale and fault on the device instead of failing cleanly. */
-#define VGPT_ABI_VERSION 5
+#define VGPT_ABI_VERSION 6
 int vgpt_abi_version(void);
 
 /* ---- transformer block -------------------------------------------------- */
@@ -109,6 +109,9 @@ int vgpt_gemm_bf16_tr(const void* A, const void* W, void* C, const void* extra, 
  * epilogues; results differ by the order of the fp32 additions inside a k-tile.  Process-wide, not thread-safe: a test and
  * measurement switch, set before the launches it is meant for.  Returns the previous value; other values change nothing. */
 int vgpt_gemm_set_family(int family);
+/* The family vgpt_gemm_set_family last set (what decides, among other things, whether vgpt_gemm_norm_workspace_bytes is
+ * non-zero); changes nothing. */
+int vgpt_gemm_get_family(void);
 
 /* RMSNorm folded into the GEMMs around it (a decoder layer's two Phi3RMSNorm calls, OmniGen/transformer.py:196-214 through
  * transformers' Phi3DecoderLayer: hidden = residual + attn(input_layernorm(hidden)); hidden = residual +

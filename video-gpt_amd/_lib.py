@@ -23,7 +23,7 @@ PRED_V, PRED_X1 = 0, 1
 _P = c_void_p
 _I64 = c_int64
 # VGPT_ABI_VERSION (include/vgpt.h) the SIGNATURES table below was written for; load() refuses any other library
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # name -> (restype, argtypes); every symbol declared in include/vgpt.h
 SIGNATURES = {
@@ -36,6 +36,7 @@ SIGNATURES = {
     "vgpt_gemm_bf16_rope": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, c_int, c_int, _P]),
     "vgpt_gemm_bf16_tr": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, c_int, c_int, c_int, _P]),
     "vgpt_gemm_set_family": (c_int, [c_int]),
+    "vgpt_gemm_get_family": (c_int, []),
     "vgpt_gemm_norm_workspace_bytes": (_I64, [_I64, _I64, _I64]),
     "vgpt_gemm_bf16_resid_rstd": (c_int, [_P, _P, _P, _P, _P, _P, _I64, c_float, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
     "vgpt_rms_rstd": (c_int, [_P, _P, _I64, _I64, _I64, c_float, _P]),

@@ -1589,22 +1589,34 @@ double w4_cost288(const GemmArgs& g, int64_t n_out) {
     return (double)cdiv(t288, cu_count()) * (1.125 * (double)(g.K / BK) + 13.5);
 }
 
+// VGPT_GEMM_W4_NI, read once: probes force the tile width (8 = 256, 6 = 192, 9 = 288 where it applies); 0 = the cost model
+int w4_forced_ni() {
+    static int forced = -1;
+    if (forced < 0) {
+        const char* e = getenv("VGPT_GEMM_W4_NI");
+        forced = e ? atoi(e) : 0;
+    }
+    return forced;
+}
+
+// 192- rather than 256-wide tiles for a product of these costs: the ONE decision behind both the launch and the partial-sum
+// count of the folded RMSNorm's workspace (norm_partials), so a forced width cannot make them disagree
+bool w4_use192(double c256, double c192) {
+    const int forced = w4_forced_ni();
+    return forced == 6 || (forced != 8 && c192 < c256);
+}
+
 template <int MODE>
 int launch_w4(const GemmArgs& g, int64_t n_out, hipStream_t s, const char* name) {
     double c256, c192;
     w4_costs<MODE>(g, n_out, c256, c192);
     const double c288 = w4_cost288<MODE>(g, n_out);
-    static int forced = -1;
-    if (forced < 0) {
-        const char* e = getenv("VGPT_GEMM_W4_NI");   // probes: force the tile width (8 = 256, 6 = 192, 9 = 288 where it applies)
-        forced = e ? atoi(e) : 0;
-    }
+    const int forced = w4_forced_ni();
     if constexpr (MODE != MODE_GATED) {
         if (c288 < 1e29 && g.ssq_out == nullptr && (forced == 9 || (forced == 0 && c288 < c256 && c288 < c192)))
             return launch_w4_cfg<MODE, 9>(g, n_out, s, name);
     }
-    const bool use192 = forced == 6 || (forced != 8 && c192 < c256);
-    if (use192) return launch_w4_cfg<MODE, 6>(g, n_out, s, name);
+    if (w4_use192(c256, c192)) return launch_w4_cfg<MODE, 6>(g, n_out, s, name);
     return launch_w4_cfg<MODE, 8>(g, n_out, s, name);
 }
 
@@ -1714,6 +1726,8 @@ VGPT_EXPORT int vgpt_gemm_set_family(int family) {
     return prev;
 }
 
+VGPT_EXPORT int vgpt_gemm_get_family(void) { return g_family; }
+
 /* ---- RMSNorm folded into the GEMMs around it ---- */
 namespace {
 // partial sums per row for this shape on the four-wave kernel; 0: not a shape it takes
@@ -1725,7 +1739,7 @@ int norm_partials(int64_t M, int64_t N, int64_t K) {
     if (g_family != 0 || forced_tile() != 0 || cdiv(M, 256) * cdiv(N, 256) < 128 || !w4_ok<MODE_PLAIN>(g, N)) return 0;
     double c256, c192;
     w4_costs<MODE_PLAIN>(g, N, c256, c192);
-    return 2 * (int)cdiv(N, c192 < c256 ? 192 : 256);
+    return 2 * (int)cdiv(N, w4_use192(c256, c192) ? 192 : 256);
 }
 int64_t norm_cnt_bytes(int64_t M) { return (cdiv(M, 256) * 4 + 255) / 256 * 256; }
 }  // namespace

@@ -78,19 +78,40 @@ def pack_left_padded(input_ids, position_ids, attention_mask, pads: List[int]):
 _FOLDED = weakref.WeakKeyDictionary()   # model -> (key, qkv weights, gate_up weights) with the RMSNorm gains folded in
 
 
+def weight_generation(model) -> int:
+    """Counter of the writes to `model`'s parameters that autograd's version counters do not see (bump_weight_generation)."""
+    return model.__dict__.get("_vgpt_weight_generation", 0)
+
+
+def bump_weight_generation(model) -> None:
+    """Called by every writer of `model`'s parameters that bypasses autograd-visible ops -- kernels writing through raw
+    pointers (Stage1Trainer's AdamW), parameters re-pointed at new storage, checkpoint loads -- so that copies derived from
+    the parameters (folded_weights) are refilled before the next sampler call reads them."""
+    model.__dict__["_vgpt_weight_generation"] = weight_generation(model) + 1
+
+
 def folded_weights(model):
     """Per decoder layer: qkv_proj.weight * input_layernorm.weight and gate_up_proj.weight * post_attention_layernorm.weight
     (per input column, rounded to bf16 once: ops.fold_norm_gain) for the per-step forward with folded RMSNorms.  Derived
-    copies (5 GB at Phi-3-mini size), built once per model and rebuilt when a parameter involved was written or replaced."""
+    copies (5 GB at Phi-3-mini size), allocated once per model and kept at their addresses (a captured graph reads them);
+    refilled in place whenever a parameter involved may have changed since: its storage or autograd version moved, or the
+    model's weight generation did (writes autograd does not see).  Checking costs 128 pointer / counter reads at 32 layers."""
     layers = model.llm.layers
     ps = [p_ for l in layers for p_ in (l.self_attn.qkv_proj.weight, l.input_layernorm.weight, l.mlp.gate_up_proj.weight,
                                         l.post_attention_layernorm.weight)]
-    key = tuple((p_.data_ptr(), p_._version) for p_ in ps)
+    key = (weight_generation(model), tuple((p_.data_ptr(), p_._version) for p_ in ps))
     hit = _FOLDED.get(model)
     if hit is not None and hit[0] == key:
         return hit[1], hit[2]
-    wq = [ops.fold_norm_gain(l.self_attn.qkv_proj.weight, l.input_layernorm.weight) for l in layers]
-    wgu = [ops.fold_norm_gain(l.mlp.gate_up_proj.weight, l.post_attention_layernorm.weight) for l in layers]
+    shapes = [(tuple(l.self_attn.qkv_proj.weight.shape), tuple(l.mlp.gate_up_proj.weight.shape)) for l in layers]
+    if hit is not None and [(tuple(a.shape), tuple(b.shape)) for a, b in zip(hit[1], hit[2])] == shapes:
+        wq, wgu = hit[1], hit[2]
+    else:
+        wq = [torch.empty_like(l.self_attn.qkv_proj.weight) for l in layers]
+        wgu = [torch.empty_like(l.mlp.gate_up_proj.weight) for l in layers]
+    for l, a, b in zip(layers, wq, wgu):
+        ops.fold_norm_gain(l.self_attn.qkv_proj.weight, l.input_layernorm.weight, out=a)
+        ops.fold_norm_gain(l.mlp.gate_up_proj.weight, l.post_attention_layernorm.weight, out=b)
     _FOLDED[model] = (key, wq, wgu)
     return wq, wgu
 
@@ -379,14 +400,26 @@ class StaticDenoiser:
     def per_clip_setup(self):
         """Everything a clip computes once instead of once per step: the MX-fp8 weights (linear_precision "fp8"), the
         condition prefix and the special rows of every step (one pass, _clip_pass; prefill() alone when the layout cannot be
-        hoisted), the final layer's adaLN modulation of every step."""
+        hoisted), the final layer's adaLN modulation of every step.  Weights derived from the parameters (the MX-fp8 records,
+        the gain-folded bf16 copies) are brought up to date with the live parameters first."""
         self.quantize_weights()
+        self.refold_weights()
         if self.S:
             if self.hoist:
                 self._clip_pass()
             else:
                 self.prefill()
         self._mod_pass()
+
+    def refold_weights(self):
+        """Folded RMSNorms: the gain-folded qkv / gate_up copies refilled in place if a parameter they come from may have
+        changed since they were folded (folded_weights); nothing to do otherwise."""
+        if self.fuse is None:
+            return
+        wq, wgu = folded_weights(self.model)
+        if wq is not self.fuse["wq"] or wgu is not self.fuse["wgu"]:   # re-allocated (other shapes): the graph read the old ones
+            self.fuse["wq"], self.fuse["wgu"] = wq, wgu
+            self.graph = None
 
     def quantize_weights(self):
         """linear_precision "fp8": every decoder layer's qkv / o / gate_up / down weights into their MX-fp8 records, from the

@@ -132,6 +132,12 @@ def linear(x: torch.Tensor, weight: torch.Tensor, residual: Optional[torch.Tenso
 
 # ---- RMSNorm folded into the GEMMs around it (include/vgpt.h: vgpt_gemm_bf16_resid_rstd -> *_prenorm) ----
 
+def gemm_family() -> int:
+    """Kernel family of the big GEMMs (include/vgpt.h vgpt_gemm_set_family): 0 = the four-wave kernel, 1 = the eight-wave
+    kernels only.  Decides, among other things, whether a shape keeps the separate RMSNorm (norm_workspace_bytes)."""
+    return int(_lib.load().vgpt_gemm_get_family())
+
+
 def norm_workspace_bytes(M: int, N: int, K: int) -> int:
     """Workspace bytes of linear_resid_rstd for this shape; 0 = the shape keeps the separate RMSNorm."""
     return int(_lib.load().vgpt_gemm_norm_workspace_bytes(M, N, K))
@@ -173,13 +179,19 @@ def rms_rstd(x: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None):
     return out
 
 
-def fold_norm_gain(weight: torch.Tensor, gain: torch.Tensor) -> torch.Tensor:
-    """weight (N, K) * gain (K) per input column, rounded to bf16 once: the Linear behind an RMSNorm with the gain folded in."""
+def fold_norm_gain(weight: torch.Tensor, gain: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """weight (N, K) * gain (K) per input column, rounded to bf16 once: the Linear behind an RMSNorm with the gain folded in.
+    `out` (N, K): refilled in place (the folded copies a captured graph reads keep their address)."""
     _chk(weight, BF16, "fold_norm_gain.weight"); _chk(gain, BF16, "fold_norm_gain.gain")
     N, K = weight.shape
     if gain.numel() != K:
         raise VgptError("fold_norm_gain: gain size mismatch")
-    out = torch.empty_like(weight)
+    if out is None:
+        out = torch.empty_like(weight)
+    else:
+        _chk(out, BF16, "fold_norm_gain.out")
+        if tuple(out.shape) != (N, K):
+            raise VgptError("fold_norm_gain: out shape mismatch")
     call("vgpt_fold_norm_gain", weight.data_ptr(), gain.data_ptr(), out.data_ptr(), N, K, _stream())
     return out
 

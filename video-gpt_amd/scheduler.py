@@ -94,6 +94,9 @@ class LVMScheduler:
                 bool(model_kwargs["use_img_cfg"]), float(model_kwargs["img_cfg_scale"]), prediction_type, tb(self.sigma),
                 self.pack_padding, self.reuse_condition_prefix, self.hoist_special_rows, self.attention_precision,
                 self.linear_precision, self.fuse_norms, str(z[0].device),
+                # the GEMM family decided whether the engine folded the RMSNorms (norm_workspace_bytes is 0 under family 1) and
+                # which kernels its graph captured: an engine of another family is not this call's
+                ops.gemm_family(),
                 # the captured graph holds the parameters' device addresses: parameters moved or re-allocated since
                 # (model.to(...), a new state dict assigned tensor by tensor) must not meet a cached graph
                 tuple(p_.data_ptr() for p_ in self._owner_params))

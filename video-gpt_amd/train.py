@@ -28,7 +28,7 @@ import torch.distributed as dist
 
 from . import ops
 from . import ops_train as T
-from .engine import _rows, count_left_pads, pack_left_padded
+from .engine import _rows, bump_weight_generation, count_left_pads, pack_left_padded
 from .ops import BF16, VgptError
 
 F32 = torch.float32
@@ -163,6 +163,7 @@ class Stage1Trainer:
             self.params[k].data = flat[o:o + sz].view(self.params[k].shape)
             o += sz
         self.param_small = flat
+        bump_weight_generation(model)     # storage re-pointed; from here on the optimizer writes it through raw pointers
         self.sumsq = torch.zeros(1, dtype=F32, device=self.dev)
         self.coef = torch.ones(1, dtype=F32, device=self.dev)
 
@@ -425,6 +426,9 @@ class Stage1Trainer:
         # master weights and moments this call is about to touch: wait for it (free in the normal flow, where the forward of
         # the step that produced these gradients already waited for every layer's event)
         self.finish_optimizer()
+        # AdamW writes the bf16 parameters through raw pointers (their autograd versions do not move): copies derived from
+        # them (engine.folded_weights) are refilled by the next sampler call, which waits for this update first
+        bump_weight_generation(self.model)
         lr = self.current_lr()
         self.last_lr = lr
         self.step_count += 1
@@ -535,6 +539,7 @@ class Stage1Trainer:
         with torch.no_grad():     # parameters are views of the flat bf16 buffers: copy in place, keep the views
             for k, p_ in own.items():
                 p_.copy_(model_sd[k])
+        bump_weight_generation(self.model)
         self.step_count = int(st["step_count"])
         if restore_hyperparameters:
             self.lr, self.wd, self.eps = float(st["lr"]), float(st["weight_decay"]), float(st["eps"])
