@@ -49,7 +49,7 @@ const char* vgpt_last_error(void);
 /* VGPT_ABI_VERSION of the library that was loaded.  Bumped with EVERY change of an exported signature; a binding written
  * for another value must refuse to call (video-gpt_amd/_lib.py does): with shifted arguments a stale library would read a
  * stream pointer as a scale and fault on the device instead of failing cleanly. */
-#define VGPT_ABI_VERSION 6
+#define VGPT_ABI_VERSION 7
 int vgpt_abi_version(void);
 
 /* ---- transformer block -------------------------------------------------- */
@@ -371,6 +371,23 @@ int vgpt_sampler_advance(int32_t* step, void* stream);
 int vgpt_sampler_copy_step_rows(const void* src, void* dst, const int32_t* step, int n_steps, int n_layers,
                                 int64_t slab_bytes, int64_t src_step_stride_bytes, int64_t src_layer_stride_bytes,
                                 int64_t dst_layer_stride_bytes, void* stream);
+/* ---- Ulysses sequence parallelism in the sampler engine (the re-layouts around the exchanges of
+ *      LVM/transform/sdpa_transform.py:125-156, where four all-to-alls of torch tensors move q, k, v and the
+ *      attention output between (B, L/P, heads, d) and (B, L, heads/P, d)) ---- */
+
+/* Split this rank's fused post-RoPE projection rows qkv (rows, (n_heads + 2 n_kv_heads) head_dim) bf16 row-major
+ * [q heads | k heads | v heads] into n_ranks chunks out (n_ranks, rows, (n_heads + 2 n_kv_heads) / n_ranks * head_dim):
+ * chunk j row t = [q heads j*n_heads/P .. | k heads j*n_kv_heads/P .. | v heads j*n_kv_heads/P ..] of row t, i.e. a fused
+ * row of rank j's heads.  One all-to-all of the chunks then carries q, k and v together.  n_heads and n_kv_heads
+ * multiples of n_ranks (VGPT_ERR_INVALID otherwise); head_dim % 8 == 0 and 16-byte aligned pointers
+ * (VGPT_ERR_UNSUPPORTED otherwise).  rows == 0 is a no-op. */
+int vgpt_sp_pack_qkv(const void* qkv, void* out, int64_t rows, int n_heads, int n_kv_heads, int head_dim, int n_ranks,
+                     void* stream);
+/* Interleave the n_ranks attention-output blocks received back (n_ranks, rows, block_width) bf16 into
+ * out (rows, n_ranks * block_width): out[t, i*block_width + c] = blocks[i, t, c] -- the heads of rank i land at their
+ * place in head order, the o_proj operand of an unsharded step.  block_width % 8 == 0, 16-byte aligned pointers. */
+int vgpt_sp_unpack_ctx(const void* blocks, void* out, int64_t rows, int64_t block_width, int n_ranks, void* stream);
+
 /* z_model = bf16(z) */
 int vgpt_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 

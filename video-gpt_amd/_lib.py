@@ -23,7 +23,7 @@ PRED_V, PRED_X1 = 0, 1
 _P = c_void_p
 _I64 = c_int64
 # VGPT_ABI_VERSION (include/vgpt.h) the SIGNATURES table below was written for; load() refuses any other library
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # name -> (restype, argtypes); every symbol declared in include/vgpt.h
 SIGNATURES = {
@@ -81,6 +81,8 @@ SIGNATURES = {
     "vgpt_sampler_advance": (c_int, [_P, _P]),
     "vgpt_sampler_copy_step_rows": (c_int, [_P, _P, _P, c_int, c_int, _I64, _I64, _I64, _I64, _P]),
     "vgpt_cast_f32_to_bf16": (c_int, [_P, _P, _I64, _P]),
+    "vgpt_sp_pack_qkv": (c_int, [_P, _P, _I64, c_int, c_int, c_int, c_int, _P]),
+    "vgpt_sp_unpack_ctx": (c_int, [_P, _P, _I64, _I64, c_int, _P]),
     "vgpt_groupnorm_stats": (c_int, [_P, _P, _I64, c_int, c_int, c_int, c_float, _P]),
     "vgpt_conv2d_fwd": (c_int, [_P] * 8 + [c_int] * 11 + [_I64, _I64, _P]),
     "vgpt_conv_bx3_packed_bytes": (c_int64, [c_int, c_int]),

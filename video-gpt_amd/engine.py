@@ -75,6 +75,24 @@ def pack_left_padded(input_ids, position_ids, attention_mask, pads: List[int]):
     return ids.contiguous(), pos.contiguous(), mask, offsets
 
 
+def sp_shares(M: int, P: int):
+    """Contiguous shares [(begin, end)] of M rows over P ranks, in rank order, and the cut granularity: shares of a
+    multiple of 256 rows (full GEMM tiles) where that keeps the largest share within 1/8 of an even split and leaves every
+    rank rows, else of 64 or 16 rows, else an even split (ragged shares differ by at most one row)."""
+    if M < P:
+        raise VgptError(f"sequence parallelism: {M} rows cannot be shared by {P} ranks")
+    even = -(-M // P)
+    for g in (256, 64, 16):
+        c = -(-even // g) * g
+        if c <= even + even // 8 and (P - 1) * c < M:
+            return [(min(r * c, M), min((r + 1) * c, M)) for r in range(P)], g
+    q, rem = divmod(M, P)
+    b = [0]
+    for r in range(P):
+        b.append(b[-1] + q + (r < rem))
+    return list(zip(b[:-1], b[1:])), 1
+
+
 _FOLDED = weakref.WeakKeyDictionary()   # model -> (key, qkv weights, gate_up weights) with the RMSNorm gains folded in
 
 
@@ -121,7 +139,8 @@ class StaticDenoiser:
                  denoise_image_sizes, time_emb_inx, n_frames: int, latent_hw, use_img_cfg: bool, img_cfg_scale: float,
                  prediction_type: str = "v", sigma: Optional[torch.Tensor] = None, pack_padding: bool = True,
                  reuse_condition_prefix: bool = False, hoist_special_rows: bool = True,
-                 attention_precision: str = "bf16", fuse_norms: Optional[bool] = None, linear_precision: str = "bf16"):
+                 attention_precision: str = "bf16", fuse_norms: Optional[bool] = None, linear_precision: str = "bf16",
+                 sequence_parallel: bool = False, sp_group=None):
         model._check_ready()
         # fuse_norms: the two RMSNorms of a decoder layer folded into the GEMMs around them in the per-step forward (ops:
         # linear_resid_ssq -> *_prenorm; include/vgpt.h).  None = on wherever the step's shapes allow it, VGPT_FUSE_NORMS=0
@@ -137,6 +156,18 @@ class StaticDenoiser:
         # activations quantised per step and weights quantised from the live parameters once per clip (per_clip_setup).  The
         # per-clip passes, embeddings, final norm and final layer stay bf16.
         self.lin_fp8 = linear_precision == "fp8"
+        # sequence_parallel: under a sequence-parallel group of P > 1 ranks (sequence_parallel.py) every rank holds about 1/P
+        # of the live rows and 1/P of the attention heads (Ulysses, LVM/model.py:457-474 + LVM/transform/sdpa_transform.py:
+        # 94-159); see _sp_plan.  Off, or with one rank: the replicated engine, unchanged.
+        from . import sequence_parallel as SPM
+        self.sp = None
+        if sequence_parallel and SPM.sp_world(sp_group) > 1:
+            for opt, val in (("attention_precision", attention_precision), ("linear_precision", linear_precision)):
+                if val != "bf16":
+                    raise VgptError(f"StaticDenoiser: {opt}={val!r} is not supported with sequence_parallel (the sharded "
+                                    "engine runs the bf16 projections and attention only)")
+            g = sp_group if sp_group is not None else SPM.get_sequence_parallel_group()
+            self.sp = {"group": g, "P": SPM.sp_world(g), "r": SPM.sp_rank(g)}
         # query rows per work item of the per-step bf16 attention: 128 = the four-wave kernel, two workgroups per CU (product).
         # 256 = the eight-wave kernel (one K / V tile staged per 256 rows: half the LDS-DMA instructions per wave and half the
         # L2 -> LDS bytes per FLOP; head dim 96): bit-identical results, measured SLOWER in round 3 -- 159.5 / 160.4 us per
@@ -290,7 +321,12 @@ class StaticDenoiser:
             self.set_sigma(sigma)
         # workspaces
         nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        if S:
+        if self.sp is not None:
+            if B != 1:
+                raise VgptError("StaticDenoiser: sequence_parallel needs one packed sequence (a batch of one, or left-padded "
+                                "rows with pack_padding=True)")
+            self._sp_plan()
+        elif S:
             Ma = self.Ma
             self.hid, self.nrm, self.ctx, self.act = e(1, Ma, H), e(1, Ma, H), e(1, Ma, nq * hd), e(1, Ma, I)
             self.qkv_full = torch.zeros(cfg.num_hidden_layers, L, (nq + 2 * nk) * hd, dtype=BF16, device=dev)
@@ -322,7 +358,7 @@ class StaticDenoiser:
                               for _ in model.llm.layers]}
             self.quantize_weights()
         elif fuse_norms:
-            Ms = self.Ma if S else B * L
+            Ms = self.sp["m"] if self.sp else (self.Ma if S else B * L)
             wa, wb = ops.norm_workspace_bytes(Ms, H, nq * hd), ops.norm_workspace_bytes(Ms, H, I)
             if wa > 0 and wb > 0:
                 wq, wgu = folded_weights(model)
@@ -352,6 +388,8 @@ class StaticDenoiser:
         step-invariant), so nothing else is needed to produce them -- leaving every layer's (post-RoPE) q/k/v in
         qkv_full[l][:S].  Rows >= S of qkv_full are written by every step (zero until the first one: the buffer is
         zero-initialised so that masked keys are finite)."""
+        if self.sp is not None:
+            return self._sp_prefill()
         m, cfg, H = self.model, self.cfg, self.H
         # with hoisting the step-invariant `<|diffusion|>` rows (right behind the prefix) are computed here as well: they
         # see the prefix and each other, nothing else
@@ -507,6 +545,8 @@ class StaticDenoiser:
         One sequence means every layer's weights stream once per clip and the GEMMs run S0 + nf + T nf rows (1.9 k at
         cfg-2 with 53 steps) instead of two passes of about half that.  Leaves qkv_full[l][:S0 + nf] (post-RoPE q/k/v of
         the cached rows) and time_qkv[step, l]."""
+        if self.sp is not None:
+            return self._sp_clip_pass()
         import numpy as np
         m, cfg, H, dev = self.model, self.cfg, self.H, self.dev
         nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
@@ -564,6 +604,240 @@ class StaticDenoiser:
         self.time_dst = self.qkv_full[:, Sc:Sc + nf]    # (layers, nf, 3H) view the step copy writes
         torch.cuda.current_stream().synchronize()
 
+    # ---- Ulysses sequence parallelism (sequence_parallel=True under a group of P > 1 ranks) ---------------------------
+    # Every pass (a step, prefill, the per-clip pass) cuts its live rows into P contiguous shares (sp_shares); rank r runs
+    # the row-local work of its share -- RMSNorm (or the folded form), qkv_proj + RoPE, o_proj + residual, gate_up + act*up,
+    # down + residual -- and the attention of its nq/P query heads (nk/P K/V heads) over ALL rows.  Per layer:
+    #   qkv rows of the share -> sp_pack_qkv -> one all-to-all -> rows of every rank for my heads, straight into the
+    #   layer's fused buffer of width (nq/P + 2 nk/P) hd behind the cached rows -> attention -> ctx rows cut by owner ->
+    #   second all-to-all -> sp_unpack_ctx -> (share, nq hd) in head order, the operand o_proj reads at P = 1.
+    # The sequence assembly (embeddings, time tokens, patch embeddings) is cheap and runs on all live rows on every rank;
+    # the share is a view of it.  After the final norm each rank runs the final layer on the frames it owns rows of and
+    # one all-gather of the predictions (owner-selected per element) leaves the full `pred` on every rank: the
+    # Euler / x1->v / CFG update runs replicated, so z stays bit-identical on all ranks.
+
+    def _sp_plan(self):
+        """Buffers of the sharded per-step forward (B == 1)."""
+        cfg, H, dev, sp = self.cfg, self.H, self.dev, self.sp
+        P, r = sp["P"], sp["r"]
+        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        if nq % P or nk % P:
+            raise VgptError(f"StaticDenoiser: sequence_parallel over {P} ranks needs num_attention_heads ({nq}) and "
+                            f"num_key_value_heads ({nk}) divisible by {P}")
+        S, L = self.S, self.L
+        Ml = L - S                                            # live rows of a step
+        shares, cut = sp_shares(Ml, P)
+        a, b = shares[r]
+        m = b - a
+        Wl = (nq // P + 2 * nk // P) * hd
+        e = lambda *s_, dt=BF16: torch.empty(*s_, dtype=dt, device=dev)
+        sp.update(shares=shares, cut=cut, a=a, b=b, m=m, Wl=Wl)
+        self.hid_all = e(1, Ml, H)                            # sequence assembly of every live row
+        self.hid = self.hid_all[:, a:b]                       # this rank's share (a contiguous view)
+        self.nrm, self.ctx, self.act = e(1, m, H), e(1, m, nq * hd), e(1, m, cfg.intermediate_size)
+        self.nrm_all = torch.zeros(1, Ml, H, dtype=BF16, device=dev)   # final norm: own rows written, the rest stays finite
+        # one fused buffer per layer behind a cached prefix (its rows are the layer's); without one every row is rewritten
+        # by every layer before it is read, so one buffer serves all layers
+        self.qkv_full = torch.zeros(cfg.num_hidden_layers if S else 1, L, Wl, dtype=BF16, device=dev)
+        self.sp_bufs = self._sp_buffers(Ml, m)
+        rope = self.rope_a if S else self.rope
+        self.sp_rope = (rope[0][a:b].contiguous(), rope[1][a:b].contiguous())
+        # the final layer: frames with a row in this share, and for every element of pred the rank that computed it
+        x_rows = [int(v) for v in (self.x_rows_a if S else self.x_rows).tolist()]
+        ntok = (self.h // 2) * (self.w // 2)
+        mine = [f for f, x0 in enumerate(x_rows) if x0 < b and x0 + ntok > a]
+        self.sp_frames = (mine[0], mine[-1] + 1) if mine else (0, 0)
+        bounds = torch.tensor([e_ for _, e_ in shares], dtype=torch.int64)
+        tok = (torch.arange(self.h)[:, None] // 2) * (self.w // 2) + torch.arange(self.w)[None, :] // 2
+        rows = torch.tensor(x_rows, dtype=torch.int64)[:, None, None] + tok[None]          # (nf, h, w) live row
+        owner = torch.bucketize(rows, bounds, right=True)                                     # share index of the row
+        C = self.pred.shape[1]
+        self.sp_owner = owner[:, None].expand(-1, C, -1, -1).reshape(1, -1).to(dev)
+        self.pred_loc = torch.zeros_like(self.pred)
+
+    def _sp_buffers(self, Mtot: int, m: int):
+        cfg, P = self.cfg, self.sp["P"]
+        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        e = lambda *s_: torch.empty(*s_, dtype=BF16, device=self.dev)
+        return {"qkv": e(m, (nq + 2 * nk) * hd), "send": e(P, m, self.sp["Wl"]), "ctx_all": e(Mtot, nq // P * hd),
+                "ctx_recv": e(P, m, nq // P * hd)}
+
+    def _sp_attention(self, bufs, shares, full, q0: int, pm, segments, ctx_out, item_rows=None):
+        """Attention of this rank's share (its q/k/v rows in bufs["qkv"]) through the two exchanges.  full: (rows, Wl) fused
+        buffer of this rank's heads; the live rows of every rank land at [q0, q0 + sum(shares)) in rank order."""
+        from . import sequence_parallel as SPM
+        cfg, sp = self.cfg, self.sp
+        P, g, Wl = sp["P"], sp["group"], sp["Wl"]
+        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        sizes = [e_ - a_ for a_, e_ in shares]
+        Mtot = sum(sizes)
+        ops.sp_pack_qkv(bufs["qkv"], P, nq, nk, hd, out=bufs["send"])
+        SPM.exchange_split(bufs["send"], full[q0:q0 + Mtot], [[n * Wl] * P for n in sizes], g)
+        Rf = full.shape[0]
+        kw = {} if item_rows is None else {"item_rows": item_rows}
+        ops.attention_qkv_range(full.view(1, Rf, Wl), pm, nq // P, nk // P, hd, q0, bufs["ctx_all"], segments=segments,
+                                **kw)
+        dc = nq // P * hd
+        SPM.exchange_split(bufs["ctx_all"], bufs["ctx_recv"], [[n * dc for n in sizes] for _ in range(P)], g)
+        ops.sp_unpack_ctx(bufs["ctx_recv"], P, out=ctx_out.view(-1, nq * hd))
+
+    def _sp_layers(self, hid, nrm, ctx, act, bufs, shares, rope, full_of, q0, pm, segments, after_qkv=None):
+        """The decoder layers of a per-clip pass on this rank's share `hid` (separate RMSNorm kernels, as the replicated
+        passes).  full_of(li): the layer's fused buffer; after_qkv(li, full): called once the layer's rows are in."""
+        m, cfg = self.model, self.cfg
+        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        for li, layer in enumerate(m.llm.layers):
+            at, mlp = layer.self_attn, layer.mlp
+            ops.rmsnorm(hid, layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=nrm)
+            ops.linear_qkv_rope(nrm, at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=bufs["qkv"])
+            full = full_of(li)
+            self._sp_attention(bufs, shares, full, q0, pm, segments, ctx)
+            if after_qkv is not None:
+                after_qkv(li, full)
+            ops.linear(ctx, at.o_proj.weight, residual=hid, out=hid)
+            ops.rmsnorm(hid, layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon, out=nrm)
+            ops.gated_mlp_act(nrm, mlp.gate_up_proj.weight, mlp.act, out=act)
+            ops.linear(act, mlp.down_proj.weight, residual=hid, out=hid)
+
+    def _sp_pass_buffers(self, Mtot: int):
+        """Share and workspaces of this rank in a per-clip pass over Mtot rows."""
+        cfg, H = self.cfg, self.H
+        shares, _ = sp_shares(Mtot, self.sp["P"])
+        a, b = shares[self.sp["r"]]
+        e = lambda *s_: torch.empty(*s_, dtype=BF16, device=self.dev)
+        mm = b - a
+        return shares, a, b, (e(1, mm, H), e(1, mm, cfg.num_attention_heads * cfg.head_dim),
+                              e(1, mm, cfg.intermediate_size)), self._sp_buffers(Mtot, mm)
+
+    def _sp_prefill(self):
+        """prefill() sharded: rows [0, S) cut into shares."""
+        m, H = self.model, self.H
+        S = self.S0 + (self.hoist["nf"] if self.hoist else 0)
+        hid_all = torch.empty(1, S, H, dtype=BF16, device=self.dev)
+        ops.embed_gather(self.input_ids[:, :S].contiguous(), m.llm.embed_tokens.weight, out=hid_all)
+        if self.cond is not None:
+            ops.patch_embed(self.cond, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, m.pos_embed[0],
+                            self.cond_rows, hid_all.view(-1, H), m.pos_embed_max_size)
+        shares, a, b, (nrm, ctx, act), bufs = self._sp_pass_buffers(S)
+        rope = (self.rope[0][a:b].contiguous(), self.rope[1][a:b].contiguous())
+        self._sp_layers(hid_all[:, a:b], nrm, ctx, act, bufs, shares, rope, lambda li: self.qkv_full[li], 0, self.pm,
+                        ((0, 0, S),))
+        torch.cuda.current_stream().synchronize()
+
+    def _sp_clip_pass(self):
+        """_clip_pass() sharded: the pass's Sc + T nf rows cut into shares; every rank keeps the cached rows and the time
+        rows of every step for its own heads."""
+        import numpy as np
+        m, cfg, H, dev = self.model, self.cfg, self.H, self.dev
+        Wl = self.sp["Wl"]
+        S0, nf, T = self.S0, self.hoist["nf"], self.num_steps
+        Sc = S0 + nf
+        Lp = Sc + T * nf
+        idx = np.concatenate([np.arange(Sc), np.tile(np.arange(Sc, Sc + nf), T)])
+        lp = self.layout.permute(idx)
+        sub = lp.sub.copy()
+        sub[0, Sc:] = 1 + np.repeat(np.arange(T), nf)
+        pm = lp.with_subgroups(sub).packed_mask(dev)
+        e = lambda *s_: torch.empty(*s_, dtype=BF16, device=dev)
+        hid_all = e(1, Lp, H)
+        ops.embed_gather(self.input_ids[:, :Sc].contiguous(), m.llm.embed_tokens.weight, out=hid_all[:, :Sc])
+        if self.cond is not None:
+            ops.patch_embed(self.cond, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, m.pos_embed[0],
+                            self.cond_rows, hid_all.view(-1, H), m.pos_embed_max_size)
+        ts = self.sigma[:T].contiguous()
+        sin, tt_h, tt_o = e(T, 256), e(T, H), e(T, H)
+        ops.timestep_sinusoid(ts, m.time_token.freqs(dev), out=sin)
+        tt = m.time_token.mlp
+        for c in range(0, T, 32):
+            ops.linear_small(sin[c:c + 32], tt[0].weight, tt[0].bias, post_act=ops.ACT_SILU, out=tt_h[c:c + 32])
+            ops.linear_small(tt_h[c:c + 32], tt[2].weight, tt[2].bias, out=tt_o[c:c + 32])
+        hid_all[0, Sc:].view(T, nf, H)[:] = tt_o[:, None, :]
+        shares, a, b, (nrm, ctx, act), bufs = self._sp_pass_buffers(Lp)
+        rope = tuple(torch.cat([t_[:Sc], t_[Sc:Sc + nf].repeat(T, 1)])[a:b].contiguous() for t_ in self.rope)
+        buf = e(Lp, Wl)
+        shape = (T, cfg.num_hidden_layers, nf, Wl)
+        if self.time_qkv is None or tuple(self.time_qkv.shape) != shape:
+            self.time_qkv = e(*shape)
+
+        def keep(li, full):
+            self.qkv_full[li][:Sc].copy_(full[:Sc])
+            self.time_qkv[:, li].copy_(full[Sc:].view(T, nf, Wl))
+        self._sp_layers(hid_all[:, a:b], nrm, ctx, act, bufs, shares, rope, lambda li: buf, 0, pm, ((0, 0, Lp),),
+                        after_qkv=keep)
+        self.time_dst = self.qkv_full[:, Sc:Sc + nf]
+        torch.cuda.current_stream().synchronize()
+
+    def _sp_forward_step(self, from_tables: bool):
+        """forward_step() sharded (see the block comment above)."""
+        from . import sequence_parallel as SPM
+        m, cfg, H, sp = self.model, self.cfg, self.H, self.sp
+        seq2d = self.hid_all.view(-1, H)
+        pos = m.pos_embed[0]
+        S = self.S
+        x_rows, t_rows = (self.x_rows_a, self.t_rows_a) if S else (self.x_rows, self.t_rows)
+        if not self.hoist:
+            ops.embed_gather(self.ids_a if S else self.input_ids, m.llm.embed_tokens.weight, out=self.hid_all)
+        if self.cond is not None and not S:
+            ops.patch_embed(self.cond, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, pos,
+                            self.cond_rows, seq2d, m.pos_embed_max_size)
+        from_tables = from_tables and self.mod_all is not None
+        if not (from_tables and self.hoist):
+            ops.timestep_sinusoid(self.ts, m.time_token.freqs(self.dev), out=self.temb_sin)
+        if self.hoist:
+            if self.time_qkv is None:
+                raise VgptError("StaticDenoiser: set_sigma() must run before the first step")
+            ops.sampler_copy_step_rows(self.time_qkv, self.time_dst, self.step)
+        else:
+            tt = m.time_token.mlp
+            ops.linear_small(self.temb_sin, tt[0].weight, tt[0].bias, post_act=ops.ACT_SILU, out=self.tt_h)
+            ops.linear_small(self.tt_h, tt[2].weight, tt[2].bias, out=seq2d, out_row=t_rows, ldo=H)
+        ops.patch_embed(self.z_model, m.x_embedder.proj.weight, m.x_embedder.proj.bias, pos, x_rows, seq2d,
+                        m.pos_embed_max_size)
+        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        fz, hid, rope, bufs = self.fuse, self.hid, self.sp_rope, self.sp_bufs
+        if fz is not None:
+            ops.rms_rstd(hid, m.llm.layers[0].input_layernorm.variance_epsilon, out=fz["rstd_in"])
+        segs = self.seg_live if S else self.seg_all
+        for li_, layer in enumerate(m.llm.layers):
+            at, mlp = layer.self_attn, layer.mlp
+            if fz is None:
+                ops.rmsnorm(hid, layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=self.nrm)
+                ops.linear_qkv_rope(self.nrm, at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=bufs["qkv"])
+            else:
+                ops.linear_qkv_rope_prenorm(hid, fz["wq"][li_], rope[0], rope[1], fz["rstd_in"], nq, nk, hd, out=bufs["qkv"])
+            self._sp_attention(bufs, sp["shares"], self.qkv_full[li_ if S else 0], S, self.pm, segs, self.ctx,
+                               item_rows=self.attn_item_rows)
+            if fz is not None:
+                ops.linear_resid_rstd(self.ctx, at.o_proj.weight, hid, fz["rstd_post"], fz["ws"],
+                                      layer.post_attention_layernorm.variance_epsilon, out=hid)
+                ops.gated_mlp_act_prenorm(hid, fz["wgu"][li_], fz["rstd_post"], mlp.act, out=self.act)
+                nxt = m.llm.layers[min(li_ + 1, len(m.llm.layers) - 1)].input_layernorm.variance_epsilon
+                ops.linear_resid_rstd(self.act, mlp.down_proj.weight, hid, fz["rstd_in"], fz["ws"], nxt, out=hid)
+                continue
+            ops.linear(self.ctx, at.o_proj.weight, residual=hid, out=hid)
+            ops.rmsnorm(hid, layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon,
+                        out=self.nrm)
+            ops.gated_mlp_act(self.nrm, mlp.gate_up_proj.weight, mlp.act, out=self.act)
+            ops.linear(self.act, mlp.down_proj.weight, residual=hid, out=hid)
+        a, b = sp["a"], sp["b"]
+        ops.rmsnorm(hid, m.llm.norm.weight, m.llm.norm.variance_epsilon, out=self.nrm_all[:, a:b])
+        if from_tables:
+            ops.sampler_copy_step_rows(self.mod_all, self.mod.view(1, self.nf, 2 * H), self.step)
+        else:
+            te = m.t_embedder.mlp
+            ops.linear_small(self.temb_sin[:1], te[0].weight, te[0].bias, post_act=ops.ACT_SILU, out=self.te_h[:1])
+            ops.linear_small(self.te_h[:1], te[2].weight, te[2].bias, out=self.temb[:1])
+            ada = m.final_layer.adaLN_modulation[1]
+            ops.linear_small(self.temb[:1], ada.weight, ada.bias, pre_act=ops.ACT_SILU, out=self.mod[:1])
+            if self.nf > 1:
+                self.mod[1:].copy_(self.mod[:1].expand(self.nf - 1, -1))
+        f0, f1 = self.sp_frames
+        if f1 > f0:
+            ops.final_layer(self.nrm_all.view(-1, H), x_rows[f0:f1], self.mod[f0:f1], m.final_layer.linear.weight,
+                            m.final_layer.linear.bias, self.pred_loc[f0:f1])
+        every = SPM.all_gather_flat(self.pred_loc, sp["group"])          # (P, elements of pred)
+        torch.gather(every, 0, self.sp_owner, out=self.pred.view(1, -1))
+
     def set_latents(self, z: torch.Tensor):
         """z: (n_frames, C, h, w) any float dtype; becomes the fp32 sampler state."""
         self.z.copy_(z.reshape(self.nf, -1).to(torch.float32))
@@ -575,6 +849,8 @@ class StaticDenoiser:
     def forward_step(self, from_tables: bool = False):
         """from_tables: the step is sigma[*step] of the table (sampler_step), so everything that depends on the step
         alone comes from the per-clip passes; otherwise `self.ts` may hold any timesteps."""
+        if self.sp is not None:
+            return self._sp_forward_step(from_tables)
         m, cfg, H = self.model, self.cfg, self.H
         seq2d = self.hid.view(-1, H)
         pos = m.pos_embed[0]
@@ -690,6 +966,8 @@ class StaticDenoiser:
 
     def capture(self):
         """Capture one sampler step into a hipGraph (must run on a non-default stream)."""
+        if self.sp is not None:
+            raise VgptError("StaticDenoiser.capture: a sequence-parallel engine runs eagerly (its exchanges are not captured)")
         # one eager step first: kernels set their attributes on first launch, which is not capturable
         saved = (self.z.clone(), self.z_model.clone(), self.step.clone())
         self.sampler_step()
@@ -705,6 +983,7 @@ class StaticDenoiser:
             raise VgptError(f"StaticDenoiser.run: {n} more steps after {self.steps_taken} exceed the {self.num_steps}-step "
                             "sigma table")
         self.steps_taken += n
+        use_graph = use_graph and self.sp is None   # sharded engines run eagerly: collectives are not captured (yet)
         if use_graph and self.graph is None and n > 0:
             # the first step runs eagerly (kernels set their launch attributes on first use, which a capture cannot
             # record) and counts as a real step; the capture that follows records without executing

@@ -730,6 +730,51 @@ def final_layer(hidden: torch.Tensor, src_row: torch.Tensor, mod: torch.Tensor, 
     return out
 
 
+# ---- Ulysses sequence parallelism (engine.StaticDenoiser, sequence_parallel=True) --------------------
+
+def sp_pack_qkv(qkv: torch.Tensor, n_ranks: int, n_heads: int, n_kv_heads: int, head_dim: int,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Ulysses pack (include/vgpt.h vgpt_sp_pack_qkv): (rows, (n_heads + 2 n_kv_heads) head_dim) post-RoPE q|k|v rows ->
+    (n_ranks, rows, (n_heads + 2 n_kv_heads) / n_ranks * head_dim), chunk j = the fused q|k|v row of rank j's heads."""
+    _chk(qkv, BF16, "sp_pack_qkv.qkv")
+    if n_ranks < 1 or n_heads % n_ranks or n_kv_heads % n_ranks:
+        raise VgptError(f"sp_pack_qkv: n_heads {n_heads} and n_kv_heads {n_kv_heads} must be multiples of n_ranks {n_ranks}")
+    W = (n_heads + 2 * n_kv_heads) * head_dim
+    if head_dim % 8 or qkv.shape[-1] != W:
+        raise VgptError(f"sp_pack_qkv: last dim {qkv.shape[-1]} != (n_heads + 2 n_kv_heads) * head_dim = {W} "
+                        "(head_dim a multiple of 8)")
+    rows = qkv.numel() // W
+    shape = (n_ranks, rows, W // n_ranks)
+    if out is None:
+        out = torch.empty(*shape, dtype=BF16, device=qkv.device)
+    else:
+        _chk(out, BF16, "sp_pack_qkv.out")
+        if tuple(out.shape) != shape:
+            raise VgptError(f"sp_pack_qkv: out is {tuple(out.shape)}, needs {shape}")
+    call("vgpt_sp_pack_qkv", qkv.data_ptr(), out.data_ptr(), rows, n_heads, n_kv_heads, head_dim, n_ranks, _stream())
+    return out
+
+
+def sp_unpack_ctx(blocks: torch.Tensor, n_ranks: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Ulysses unpack (include/vgpt.h vgpt_sp_unpack_ctx): (n_ranks, rows, Dc) attention-output head blocks received back
+    -> (rows, n_ranks * Dc) in head order."""
+    _chk(blocks, BF16, "sp_unpack_ctx.blocks")
+    if n_ranks < 1 or blocks.dim() != 3 or blocks.shape[0] != n_ranks:
+        raise VgptError(f"sp_unpack_ctx: blocks {tuple(blocks.shape)} are not ({n_ranks}, rows, block_width)")
+    Dc = blocks.shape[-1]
+    if Dc % 8:
+        raise VgptError(f"sp_unpack_ctx: block width {Dc} must be a multiple of 8")
+    rows = blocks.shape[1]
+    if out is None:
+        out = torch.empty(rows, n_ranks * Dc, dtype=BF16, device=blocks.device)
+    else:
+        _chk(out, BF16, "sp_unpack_ctx.out")
+        if out.shape[-1] != n_ranks * Dc or out.numel() != rows * n_ranks * Dc:
+            raise VgptError(f"sp_unpack_ctx: out {tuple(out.shape)} is not ({rows}, {n_ranks * Dc}) (leading dims may be split)")
+    call("vgpt_sp_unpack_ctx", blocks.data_ptr(), out.data_ptr(), rows, Dc, n_ranks, _stream())
+    return out
+
+
 # ---- sampler ----------------------------------------------------------------------------------
 
 def sampler_set_timesteps(sigma: torch.Tensor, step: torch.Tensor, timesteps: torch.Tensor):

@@ -42,6 +42,7 @@ class LVMPipeline:
         self.mask_format = "layout"   # "bool": have the collator paint the reference's dense (B,L,L) mask instead
         self.attention_precision = "bf16"   # "fp8": MX-fp8 attention in the sampler steps (scheduler.LVMScheduler)
         self.linear_precision = "bf16"      # "fp8": MX-fp8 decoder-layer projections in the sampler steps (scheduler.LVMScheduler)
+        self.sequence_parallel_engine = False   # True: sharded sampler engine under a sequence-parallel group (scheduler.LVMScheduler)
 
     @classmethod
     def from_pretrained(cls, model_name, vae_path: str = None, load_llm_ckpt=True):
@@ -182,6 +183,7 @@ class LVMPipeline:
             scheduler = LVMScheduler(num_steps=num_inference_steps, time_shifting_factor=time_shifting_factor)
             scheduler.attention_precision = self.attention_precision
             scheduler.linear_precision = self.linear_precision
+            scheduler.sequence_parallel_engine = self.sequence_parallel_engine
             samples = scheduler(latents, self.model.forward_with_cfg, model_kwargs, use_kv_cache=use_kv_cache,
                                 offload_kv_cache=offload_kv_cache, prediction_type=prediction_type, vae=self.vae)
             samples = samples.chunk(1 + num_cfg, dim=0)[0]
@@ -289,6 +291,7 @@ class LVMPipeline:
             scheduler = LVMScheduler(num_steps=num_inference_steps, time_shifting_factor=time_shifting_factor)
             scheduler.attention_precision = self.attention_precision
             scheduler.linear_precision = self.linear_precision
+            scheduler.sequence_parallel_engine = self.sequence_parallel_engine
             samples = scheduler(latents, self.model.frame_block_forward_with_cfg, model_kwargs,
                                 use_kv_cache=use_kv_cache, offload_kv_cache=offload_kv_cache,
                                 prediction_type=prediction_type, vae=self.vae)

@@ -38,6 +38,11 @@ class LVMScheduler:
         self.attention_precision = "bf16"    # "fp8": MX-fp8 attention in the sampler steps of the fast path (cfg-5 option)
         self.linear_precision = "bf16"       # "fp8": MX-fp8 qkv / o / gate_up / down projections in the fast path's steps
         self.fuse_norms = None               # None: RMSNorms folded into the GEMMs wherever the step's shapes allow (engine.py); False: never
+        # True: under a sequence-parallel group of P > 1 ranks (sequence_parallel.py) the fast path builds the sharded engine
+        # (Ulysses: every rank runs ~1/P of the live rows and 1/P of the attention heads, engine.StaticDenoiser._sp_plan).
+        # Sharded engines run eagerly, whatever use_graph says: capturing the RCCL exchanges into a hipGraph is a separate
+        # step.  False (default): every rank runs the whole clip, as before.
+        self.sequence_parallel_engine = False
         # keep the engine of a clip on the model and re-use it for the next clip of an identical sequence (the rounds of a
         # rollout once the window is full: LVM/pipeline.py:418-422 re-creates the same prompt every round): buffers, attention
         # plan and the captured graph survive, the per-clip pass is redone on the new condition latents
@@ -82,6 +87,7 @@ class LVMScheduler:
     def _engine_key(self, z, model_kwargs, prediction_type):
         """Everything a StaticDenoiser is built from except the condition latents' VALUES; None when the mask is not a
         TokenLayout (a dense mask would have to be compared element by element)."""
+        from . import sequence_parallel as SPM
         from .layout import TokenLayout
         mask = model_kwargs["attention_mask"]
         if not isinstance(mask, TokenLayout):
@@ -94,6 +100,8 @@ class LVMScheduler:
                 bool(model_kwargs["use_img_cfg"]), float(model_kwargs["img_cfg_scale"]), prediction_type, tb(self.sigma),
                 self.pack_padding, self.reuse_condition_prefix, self.hoist_special_rows, self.attention_precision,
                 self.linear_precision, self.fuse_norms, str(z[0].device),
+                # a sharded engine holds this rank's rows and heads of a group of this size
+                self.sequence_parallel_engine, SPM.sp_world(), SPM.sp_rank(),
                 # the GEMM family decided whether the engine folded the RMSNorms (norm_workspace_bytes is 0 under family 1) and
                 # which kernels its graph captured: an engine of another family is not this call's
                 ops.gemm_family(),
@@ -110,7 +118,7 @@ class LVMScheduler:
                               reuse_condition_prefix=self.reuse_condition_prefix,
                               hoist_special_rows=self.hoist_special_rows,
                               attention_precision=self.attention_precision, linear_precision=self.linear_precision,
-                              fuse_norms=self.fuse_norms)
+                              fuse_norms=self.fuse_norms, sequence_parallel=self.sequence_parallel_engine)
 
     def __call__(self, z, func, model_kwargs, use_kv_cache: bool = True, offload_kv_cache: bool = True,
                  prediction_type: str = "v", vae=None, noise_level=None):
@@ -134,6 +142,11 @@ class LVMScheduler:
             # the fp8 projections exist in the engine's per-step forward only: no silent bf16 run of another path
             raise VgptError(f"LVMScheduler: linear_precision={self.linear_precision!r} needs the fast path (StaticDenoiser: "
                             "frame_block_forward_with_cfg of this package on a list of equal-shape latents)")
+        if engine is None and self.sequence_parallel_engine:
+            from . import sequence_parallel as SPM
+            if SPM.sp_world() > 1:   # no silent replicated run of the whole clip on every rank
+                raise VgptError("LVMScheduler: sequence_parallel_engine=True needs the fast path (StaticDenoiser: "
+                                "frame_block_forward_with_cfg of this package on a list of equal-shape latents)")
         if engine is not None:
             self.last_engine = engine
             stream = torch.cuda.current_stream()

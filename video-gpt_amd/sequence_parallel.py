@@ -128,3 +128,50 @@ def gather_sequence(hidden: torch.Tensor, group=None) -> torch.Tensor:
         dist.all_gather(hp, host, group=group)
         parts = [t.to(hidden.device) for t in hp]
     return torch.cat(parts, dim=1)
+
+
+# ---- exchanges of the sharded sampler engine (engine.StaticDenoiser with sequence_parallel=True) ----
+
+def exchange_split(send: torch.Tensor, recv: torch.Tensor, counts, group=None) -> torch.Tensor:
+    """All-to-all with per-rank split sizes, in place: counts[i][j] = elements rank i sends to rank j (every rank passes
+    the same matrix); `send` holds this rank's chunks in destination order, `recv` (contiguous) receives the chunks of
+    ranks 0..P-1 in rank order.  RCCL: one all_to_all_single on the current stream.  Other transports (gloo, the tests'
+    two ranks on one GPU): an all-gather of padded buffers through host memory -- test-only bandwidth."""
+    group = group if group is not None else _GROUP
+    P, me = dist.get_world_size(group), dist.get_rank(group)
+    if len(counts) != P or any(len(row) != P for row in counts):
+        raise ValueError(f"exchange_split: counts must be a {P} x {P} matrix")
+    rs = [int(counts[i][me]) for i in range(P)]
+    if send.numel() != sum(counts[me]) or recv.numel() != sum(rs) or not recv.is_contiguous():
+        raise ValueError("exchange_split: send / recv sizes disagree with counts (recv must be contiguous)")
+    if dist.get_backend(group) == "nccl":
+        dist.all_to_all_single(recv.view(-1), send.contiguous().view(-1), output_split_sizes=rs,
+                               input_split_sizes=[int(c) for c in counts[me]], group=group)
+        return recv
+    es = send.element_size()                      # moved as bytes: any dtype, whatever the transport supports
+    n = max(sum(row) for row in counts) * es
+    host = torch.zeros(n, dtype=torch.uint8)
+    host[:send.numel() * es] = send.reshape(-1).cpu().view(torch.uint8)
+    gathered = [torch.empty_like(host) for _ in range(P)]
+    dist.all_gather(gathered, host, group=group)
+    parts = []
+    for i in range(P):
+        off = sum(counts[i][:me]) * es
+        parts.append(gathered[i][off:off + rs[i] * es])
+    recv.view(-1).copy_(torch.cat(parts).view(recv.dtype).to(recv.device))
+    return recv
+
+
+def all_gather_flat(x: torch.Tensor, group=None) -> torch.Tensor:
+    """(P, x.numel()) stack of every rank's `x` (same size on every rank), row i from rank i."""
+    group = group if group is not None else _GROUP
+    P = dist.get_world_size(group)
+    flat = x.contiguous().view(-1)
+    if dist.get_backend(group) == "nccl":
+        out = torch.empty(P, flat.numel(), dtype=x.dtype, device=x.device)
+        dist.all_gather_into_tensor(out, flat, group=group)
+        return out
+    host = flat.cpu().view(torch.uint8)
+    hp = [torch.empty_like(host) for _ in range(P)]
+    dist.all_gather(hp, host, group=group)
+    return torch.stack(hp).view(x.dtype).to(x.device)
