@@ -49,7 +49,7 @@ const char* vgpt_last_error(void);
 /* VGPT_ABI_VERSION of the library that was loaded.  Bumped with EVERY change of an exported signature; a binding written
  * for another value must refuse to call (video-gpt_amd/_lib.py does): with shifted arguments a stale library would read a
  * stream pointer as a scale and fault on the device instead of failing cleanly. */
-#define VGPT_ABI_VERSION 7
+#define VGPT_ABI_VERSION 8
 int vgpt_abi_version(void);
 
 /* ---- transformer block -------------------------------------------------- */
@@ -510,10 +510,13 @@ int vgpt_embed_bwd(const int64_t* ids, const uint8_t* keep, const void* dseq, fl
 int vgpt_patchify(const void* x, void* patches, int n_frames, int C, int h, int w, void* stream);
 int vgpt_unpatchify_bwd(const void* dpred, void* dy16, int n_frames, int C, int h, int w, void* stream);
 int vgpt_gather_rows(const void* in, const int32_t* row0, void* out, int n_seg, int per, int64_t H, void* stream);
-/* *out += sum g^2 (deterministic two-stage reduction: replicas must agree bit for bit);  coef = min(1, max_norm/(sqrt(sumsq)+1e-6)) * extra_scale;  AdamW on fp32 master weights
- * (torch.optim.AdamW update; bf16 model copy refreshed; *grad_scale multiplies the gradient). */
+/* *out += sum g^2 (deterministic two-stage reduction: replicas must agree bit for bit);  coef = min(1, max_norm/(sqrt(S)+1e-6)) * extra_scale
+ * with S the sum of the n >= 1 values sumsq[0..n-1] (per-rank partial sums of a sharded optimizer, in rank order), added in
+ * a fixed order (n == 1: S = sumsq[0]); *norm_out (may be NULL) = sqrt(S); n < 1 or a NULL sumsq / coef: VGPT_ERR_INVALID;
+ * AdamW on fp32 master weights (torch.optim.AdamW update; bf16 model copy refreshed; *grad_scale multiplies the gradient). */
 int vgpt_sumsq(const void* g, int g_f32, float* out, int64_t n, float* partial_ws /* >= 1024 floats */, void* stream);
-int vgpt_clip_coef(const float* sumsq, float* coef, float* norm_out, float max_norm, float extra_scale, void* stream);
+int vgpt_clip_coef(const float* sumsq, int n, float* coef, float* norm_out, float max_norm, float extra_scale,
+                   void* stream);
 int vgpt_adamw_step(float* master, void* param, const void* grad, int grad_f32, float* m, float* v, int64_t n, float lr,
                     float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale,
                     void* stream);

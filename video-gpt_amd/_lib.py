@@ -23,7 +23,7 @@ PRED_V, PRED_X1 = 0, 1
 _P = c_void_p
 _I64 = c_int64
 # VGPT_ABI_VERSION (include/vgpt.h) the SIGNATURES table below was written for; load() refuses any other library
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 # name -> (restype, argtypes); every symbol declared in include/vgpt.h
 SIGNATURES = {
@@ -119,7 +119,7 @@ SIGNATURES = {
     "vgpt_unpatchify_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "vgpt_gather_rows": (c_int, [_P, _P, _P, c_int, c_int, _I64, _P]),
     "vgpt_sumsq": (c_int, [_P, c_int, _P, _I64, _P, _P]),
-    "vgpt_clip_coef": (c_int, [_P, _P, _P, c_float, c_float, _P]),
+    "vgpt_clip_coef": (c_int, [_P, c_int, _P, _P, c_float, c_float, _P]),
     "vgpt_adamw_step": (c_int, [_P, _P, _P, c_int, _P, _P, _I64, c_float, c_float, c_float, c_float, c_float, c_int,
                                 _P, _P]),
     "vgpt_graph_begin_capture": (c_int, [_P]),

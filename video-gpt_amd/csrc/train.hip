@@ -589,9 +589,16 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, 
     }
 }
 
-// clip coefficient: coef = min(1, max_norm / (sqrt(sumsq) + 1e-6)) * extra_scale
-__global__ void clip_coef_kernel(const float* sumsq, float* coef, float* norm_out, float max_norm, float extra) {
-    const float nrm = sqrtf(*sumsq);
+// clip coefficient over n sums of squares (one per data-parallel shard, in rank order): one wave, lane i adds values i,
+// i+64, ... in order, then the fixed shuffle tree of sumsq_final_kernel, so every rank computes the same bits from the
+// same n values; coef = min(1, max_norm / (sqrt(sum) + 1e-6)) * extra_scale.  n == 1: the sum is sumsq[0] exactly.
+__global__ __launch_bounds__(64) void clip_coef_kernel(const float* __restrict__ sumsq, int n, float* coef, float* norm_out,
+                                                       float max_norm, float extra) {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += 64) s += sumsq[i];
+    s = wave_sum(s);
+    if (threadIdx.x != 0) return;
+    const float nrm = sqrtf(s);
     if (norm_out) *norm_out = nrm;
     float c = max_norm > 0.f ? max_norm / (nrm + 1e-6f) : 1.0f;
     *coef = fminf(c, 1.0f) * extra;
@@ -868,10 +875,11 @@ VGPT_EXPORT int vgpt_sumsq(const void* g, int g_f32, float* out, int64_t n, floa
     LAUNCH_OK("vgpt_sumsq");
 }
 
-VGPT_EXPORT int vgpt_clip_coef(const float* sumsq, float* coef, float* norm_out, float max_norm, float extra_scale,
-                               void* stream) {
+VGPT_EXPORT int vgpt_clip_coef(const float* sumsq, int n, float* coef, float* norm_out, float max_norm,
+                               float extra_scale, void* stream) {
     VGPT_REQUIRE(sumsq && coef, VGPT_ERR_INVALID, "vgpt_clip_coef: null pointer");
-    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sumsq, coef, norm_out, max_norm,
+    VGPT_REQUIRE(n >= 1, VGPT_ERR_INVALID, "vgpt_clip_coef: n must be >= 1");
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sumsq, n, coef, norm_out, max_norm,
                        extra_scale);
     LAUNCH_OK("vgpt_clip_coef");
 }

@@ -203,8 +203,11 @@ def sumsq(g, out):
 
 
 def clip_coef(sumsq_t, coef, norm_out, max_norm, extra_scale=1.0):
-    call("vgpt_clip_coef", sumsq_t.data_ptr(), coef.data_ptr(), _ptr(norm_out), float(max_norm), float(extra_scale),
-         _stream())
+    """sumsq_t: (n,) fp32 sums of squares (n > 1: one per rank of a sharded optimizer, rank order), added on the device."""
+    if not sumsq_t.is_cuda or sumsq_t.dtype != F32 or not sumsq_t.is_contiguous():
+        raise VgptError("clip_coef: sumsq must be a contiguous fp32 GPU tensor")
+    call("vgpt_clip_coef", sumsq_t.data_ptr(), sumsq_t.numel(), coef.data_ptr(), _ptr(norm_out), float(max_norm),
+         float(extra_scale), _stream())
 
 
 def adamw_step(master, param, grad, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=None):

@@ -130,7 +130,8 @@ def gather_sequence(hidden: torch.Tensor, group=None) -> torch.Tensor:
     return torch.cat(parts, dim=1)
 
 
-# ---- exchanges of the sharded sampler engine (engine.StaticDenoiser with sequence_parallel=True) ----
+# ---- flat exchanges: the sharded sampler engine (engine.StaticDenoiser with sequence_parallel=True) and the trainer's
+#      sharded optimizer (train.Stage1Trainer with dp_sharding="optimizer") ----
 
 def exchange_split(send: torch.Tensor, recv: torch.Tensor, counts, group=None) -> torch.Tensor:
     """All-to-all with per-rank split sizes, in place: counts[i][j] = elements rank i sends to rank j (every rank passes
@@ -162,16 +163,43 @@ def exchange_split(send: torch.Tensor, recv: torch.Tensor, counts, group=None) -
     return recv
 
 
-def all_gather_flat(x: torch.Tensor, group=None) -> torch.Tensor:
-    """(P, x.numel()) stack of every rank's `x` (same size on every rank), row i from rank i."""
+def _flat_collective(fn, out: torch.Tensor, inp: torch.Tensor, group, async_op: bool):
+    """fn(out, inp) -- dist.all_gather_into_tensor or dist.reduce_scatter_tensor -- on the device tensors over RCCL (`inp`
+    may be this rank's slice of `out`: in place; with async_op the work handle is returned).  Other transports (gloo, the
+    tests' ranks sharing one GPU) have no device-tensor version: the collective runs on host copies and the result is
+    copied back on the current stream before returning (None) -- test-only bandwidth."""
+    if dist.get_backend(group) == "nccl":
+        return fn(out, inp, group=group, async_op=async_op)
+    host = torch.empty(out.shape, dtype=out.dtype)
+    fn(host, inp.cpu(), group=group)
+    out.copy_(host)
+    return None
+
+
+def all_gather_flat(x: torch.Tensor, group=None, out: Optional[torch.Tensor] = None, async_op: bool = False):
+    """(P, x.numel()) stack of every rank's `x` (same size on every rank), row i from rank i.  `out` (contiguous, P x
+    x.numel() elements) receives it instead of a new tensor; `x` may be row `rank` of `out` (in place).  async_op: the
+    RCCL work handle is returned instead (None on host-staged transports, which finish before returning)."""
     group = group if group is not None else _GROUP
     P = dist.get_world_size(group)
     flat = x.contiguous().view(-1)
-    if dist.get_backend(group) == "nccl":
+    if out is None:
         out = torch.empty(P, flat.numel(), dtype=x.dtype, device=x.device)
-        dist.all_gather_into_tensor(out, flat, group=group)
-        return out
-    host = flat.cpu().view(torch.uint8)
-    hp = [torch.empty_like(host) for _ in range(P)]
-    dist.all_gather(hp, host, group=group)
-    return torch.stack(hp).view(x.dtype).to(x.device)
+    if out.numel() != P * flat.numel() or not out.is_contiguous():
+        raise ValueError("all_gather_flat: out must be contiguous with P x x.numel() elements")
+    work = _flat_collective(dist.all_gather_into_tensor, out.view(-1), flat, group, async_op)
+    return work if async_op else out.view(P, flat.numel())
+
+
+def reduce_scatter_flat(buf: torch.Tensor, group=None, async_op: bool = False):
+    """In place on the contiguous flat `buf` (numel a multiple of P): rank r's slice [r*s, (r+1)*s), s = numel / P,
+    receives the sum over the ranks of that slice; the rest of `buf` keeps this rank's values.  Returns the slice, or
+    with async_op the RCCL work handle (None on host-staged transports, which finish before returning)."""
+    group = group if group is not None else _GROUP
+    P, me = dist.get_world_size(group), dist.get_rank(group)
+    if buf.dim() != 1 or not buf.is_contiguous() or buf.numel() % P:
+        raise ValueError(f"reduce_scatter_flat: need a contiguous 1-D buffer whose length is a multiple of {P}")
+    s = buf.numel() // P
+    mine = buf[me * s:(me + 1) * s]
+    work = _flat_collective(dist.reduce_scatter_tensor, mine, buf, group, async_op)
+    return work if async_op else mine

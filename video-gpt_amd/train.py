@@ -10,9 +10,11 @@ optimizer to DeepSpeed's bf16 AdamW (fp32 master weights).  Here:
   * every backward pass is a HIP kernel (ops_train.py); the big dX / dW products reuse the MFMA NT GEMM
     through padded transposes, attention has its own dQ / dKdV kernels;
   * data parallelism replicates the model (288 GB HBM holds params + fp32 master + Adam moments, ~60 GB
-    at Phi-3-mini size; no ZeRO sharding) and all-reduces one flat bf16 gradient bucket per decoder
-    layer (226 MB at full size) as soon as that layer's backward has produced it, on RCCL's stream,
-    while the next layer's backward runs; the small fp32 gradients go in one last bucket;
+    at Phi-3-mini size) and all-reduces one flat bf16 gradient bucket per decoder layer (226 MB at full
+    size) as soon as that layer's backward has produced it, on RCCL's stream, while the next layer's
+    backward runs; the small fp32 gradients go in one last bucket.  dp_sharding="optimizer" (ZeRO stage 1
+    on the reference's stage-2 exchange) reduce-scatters those buckets instead, keeps the fp32 master
+    weights and moments of this rank's shard only and all-gathers the updated bf16 parameters;
   * clipping uses the norm of the averaged gradient; the 1/world factor and the clip coefficient are
     folded into the AdamW kernel's gradient scale (no separate pass over the gradients).
 """
@@ -28,10 +30,28 @@ import torch.distributed as dist
 
 from . import ops
 from . import ops_train as T
+from . import sequence_parallel as SPM
 from .engine import _rows, bump_weight_generation, count_left_pads, pack_left_padded
 from .ops import BF16, VgptError
 
 F32 = torch.float32
+DP_SHARDING_MODES = ("none", "optimizer")
+# dp_sharding="optimizer": every flat bucket is padded to a multiple of world * SHARD_GRANULE elements, so each rank's
+# shard starts 512 (bf16) / 1024 (fp32) bytes apart: vgpt_adamw_step's alignment check and vgpt_sumsq's 16-byte loads
+SHARD_GRANULE = 256
+
+
+def shard_partition(n: int, world: int):
+    """(padded length, shard length s) of a flat bucket of n elements sharded over `world` ranks: rank r owns
+    [r * s, (r + 1) * s) of the zero-padded bucket.  The padded length is the smallest multiple of world * SHARD_GRANULE
+    that holds n; at world 1 it is n itself (no padding)."""
+    if world < 1 or n < 0:
+        raise VgptError(f"shard_partition: bad bucket length {n} or world size {world}")
+    if world == 1:
+        return n, n
+    g = world * SHARD_GRANULE
+    padded = -(-n // g) * g
+    return padded, padded // world
 
 
 _TRAINER_OF = weakref.WeakKeyDictionary()   # model -> weakref to the trainer whose optimizer updates it on a stream of its own
@@ -39,8 +59,9 @@ _TRAINER_OF = weakref.WeakKeyDictionary()   # model -> weakref to the trainer wh
 
 def wait_for_pending_update(model) -> None:
     """Readers of `model`'s parameters outside Stage1Trainer.step() -- the sampler (validation clips through LVMPipeline),
-    state_dict() -- call this: with `overlap_optimizer` the last AdamW update may still be running on the trainer's own stream.
-    Makes the CURRENT stream wait for it; nothing to do otherwise."""
+    state_dict() -- call this: with `overlap_optimizer` the last AdamW update may still be running on the trainer's own stream,
+    with dp_sharding="optimizer" the all-gathers of the updated parameters may still be in flight.
+    Makes the CURRENT stream wait for them; nothing to do otherwise."""
     ref = _TRAINER_OF.get(model)
     tr = ref() if ref is not None else None
     if tr is not None:
@@ -56,7 +77,7 @@ class Stage1Trainer:
                  max_grad_norm: Optional[float] = 1.0, input_noise: float = 0.9, pack_padding: bool = True,
                  lr_scheduler: str = "constant", lr_warmup_steps: int = 0, gradient_checkpointing: Optional[bool] = None,
                  forward_only: bool = False, lr_scheduler_steps_per_optimizer_step: int = 1,
-                 overlap_optimizer: bool = False):
+                 overlap_optimizer: bool = False, dp_sharding: Optional[str] = None):
         """lr_scheduler / lr_warmup_steps: diffusers' get_scheduler("constant" | "constant_with_warmup")
         (train_x1_stage1_noiseinput.py:279-283; the scripts use constant_with_warmup): the k-th optimizer step (k = 0, 1,
         ...) runs at lr * min(1, k * lr_scheduler_steps_per_optimizer_step / warmup).
@@ -70,7 +91,10 @@ class Stage1Trainer:
         deepspeed, absent here): parity of the warm-up length is unpinned.  gradient_checkpointing (default: model.llm.gradient_checkpointing, set by
         `model.llm.gradient_checkpointing_enable()`, train...py:170-171): keep only each decoder layer's input and
         recompute the layer inside the backward (OmniGen/transformer.py:182-192).  forward_only: no gradient / optimizer
-        state (loss evaluation through `loss.training_losses_x1_noise_input`)."""
+        state (loss evaluation through `loss.training_losses_x1_noise_input`).  dp_sharding (default: $VGPT_DP_SHARDING,
+        else "none"): "none" replicates the fp32 optimizer state on every rank and all-reduces the gradients; "optimizer"
+        shards it (reduce-scatter of the gradient buckets, AdamW on this rank's 1/world of every bucket, all-gather of the
+        updated parameters).  Inert at world size 1."""
         model._check_ready()
         if hasattr(model, "release_engines"):
             model.release_engines()          # a sampler engine cached on the model holds GBs the trainer's buffers want
@@ -90,19 +114,29 @@ class Stage1Trainer:
         self.input_noise = input_noise
         self.pack_padding = pack_padding
         self.dev = model.llm.norm.weight.device
+        self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        self.rank = dist.get_rank() if self.world > 1 else 0
+        if dp_sharding is None:
+            dp_sharding = os.environ.get("VGPT_DP_SHARDING", "none")
+        if dp_sharding not in DP_SHARDING_MODES:
+            raise VgptError(f"dp_sharding {dp_sharding!r}: expected one of {DP_SHARDING_MODES}")
+        self.dp_sharding = dp_sharding
+        self._sharded = dp_sharding == "optimizer" and self.world > 1 and not forward_only
+        self._group = dist.group.WORLD if self.world > 1 else None
+        self._gathers = None         # (small, [layer 0 .. nl-1]) all-gathers of updated parameters in flight (sharded)
         # AdamW behind the clip coefficient on a stream of its own (see optimizer_step): events of the update of the small
         # bucket and of every layer bucket, waited for where the next forward first reads those parameters
         self.overlap_optimizer = bool(overlap_optimizer) and self.dev.type == "cuda" and not forward_only
         self._opt_stream = torch.cuda.Stream(device=self.dev) if self.overlap_optimizer else None
-        if self.overlap_optimizer:
-            # parameters are read outside step() too: the sampler asks wait_for_pending_update(model), state_dict() through
-            # this hook
+        if self.overlap_optimizer or self._sharded:
+            # parameters are read outside step() too, and may still be updated (overlap_optimizer) or all-gathered (sharded):
+            # the sampler asks wait_for_pending_update(model), state_dict() through this hook
             _TRAINER_OF[model] = weakref.ref(self)
             model.register_state_dict_pre_hook(_state_dict_barrier)
         self._opt_events = None      # (small, [layer 0 .. nl-1]) of the update in flight
         self.step_count = 0
-        self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-        self.skip_allreduce = False   # measurement only (bench.py's exposed-communication leg): ranks stop agreeing when set
+        self.skip_allreduce = False   # measurement only (bench.py's exposed-communication leg): ranks stop agreeing when set;
+        #                               skips every collective of the step (sharded: reduce-scatter, norm exchange, all-gather)
         # VGPT_DP_OVERLAP=0: all buckets are reduced behind the backward instead of layer by layer under it (for A/B runs on a
         # multi-GPU node: RCCL's kernels share the CUs with the backward's GEMMs while they overlap)
         self.overlap_allreduce = os.environ.get("VGPT_DP_OVERLAP", "1") != "0"
@@ -118,9 +152,11 @@ class Stage1Trainer:
                              f"llm.layers.{i}.mlp.gate_up_proj.weight", f"llm.layers.{i}.mlp.down_proj.weight"]
                             for i in range(L)]
         self.layer_buckets = []
+        self._bucket_numel = []       # unpadded lengths of the layer buckets: the checkpoint layout
         for names in self.layer_names:
             n = sum(self.params[k].numel() for k in names)
-            flat = torch.zeros(n, dtype=BF16, device=self.dev)
+            self._bucket_numel.append(n)
+            flat = torch.zeros(self._padded(n), dtype=BF16, device=self.dev)
             o = 0
             for k in names:
                 sz = self.params[k].numel()
@@ -130,12 +166,16 @@ class Stage1Trainer:
         big = {k for names in self.layer_names for k in names}
         small = [k for k in self.params if k not in big]
         n_small = sum(self.params[k].numel() for k in small)
-        self.small_bucket = torch.zeros(n_small, dtype=F32, device=self.dev)
+        self._small_numel = n_small
+        self.small_bucket = torch.zeros(self._padded(n_small), dtype=F32, device=self.dev)
         o = 0
         for k in small:
             sz = self.params[k].numel()
             self.grads[k] = self.small_bucket[o:o + sz].view(self.params[k].shape)
             o += sz
+        if self._sharded:
+            self._init_sharded_state(small)
+            return
         # ---- optimizer state (fp32 master + moments), flat per bucket so AdamW is one launch per bucket ----
         def flat_params(names):
             return torch.cat([self.params[k].detach().reshape(-1).to(F32) for k in names])
@@ -164,10 +204,68 @@ class Stage1Trainer:
             o += sz
         self.param_small = flat
         bump_weight_generation(model)     # storage re-pointed; from here on the optimizer writes it through raw pointers
+        self._init_scalars()
+
+    def _init_scalars(self):
         self.sumsq = torch.zeros(1, dtype=F32, device=self.dev)
         self.coef = torch.ones(1, dtype=F32, device=self.dev)
 
         self.grad_norm = torch.zeros(1, dtype=F32, device=self.dev)
+
+    # ---- dp_sharding="optimizer" -----------------------------------------------------------------------------------
+    def _padded(self, n: int) -> int:
+        return shard_partition(n, self.world)[0] if self._sharded else n
+
+    def _shard(self, flat: torch.Tensor) -> torch.Tensor:
+        """This rank's contiguous slice of a padded flat bucket (the whole bucket when not sharded)."""
+        if not self._sharded:
+            return flat
+        s = flat.numel() // self.world
+        return flat[self.rank * s:(self.rank + 1) * s]
+
+    def _init_sharded_state(self, small):
+        """Parameters become views into the front of zero-padded flat bf16 buckets (padded like the gradient buckets);
+        fp32 master weights and moments exist for this rank's shard of every bucket only, the master shard taken from the
+        parameter shard.  No full-length fp32 temporary: at full size it would be the replicated state this mode avoids."""
+        def flat_params(names):
+            n = sum(self.params[k].numel() for k in names)
+            flat = torch.zeros(self._padded(n), dtype=self.params[names[0]].dtype, device=self.dev)
+            o = 0
+            for k in names:
+                sz = self.params[k].numel()
+                flat[o:o + sz].copy_(self.params[k].detach().reshape(-1))
+                self.params[k].data = flat[o:o + sz].view(self.params[k].shape)
+                o += sz
+            return flat
+        self.param_layers = [flat_params(names) for names in self.layer_names]
+        self.param_small = flat_params(small)
+        self.small_names = small
+        self.master_layers = [self._shard(b).to(F32) for b in self.param_layers]
+        self.master_small = self._shard(self.param_small).to(F32)
+        z = lambda t: torch.zeros_like(t)
+        self.m_layers = [z(t) for t in self.master_layers]
+        self.v_layers = [z(t) for t in self.master_layers]
+        self.m_small, self.v_small = z(self.master_small), z(self.master_small)
+        bump_weight_generation(self.model)
+        self._init_scalars()
+        self._partials = torch.zeros(self.world, dtype=F32, device=self.dev)   # every rank's sum of squares, rank order
+
+    def _reduce(self, bucket):
+        """Asynchronous gradient exchange of one flat bucket: all-reduce (replicated), or a reduce-scatter whose sum lands in
+        this rank's own slice of the bucket (sharded).  None when a host-staged transport has already finished it."""
+        if self._sharded:
+            return SPM.reduce_scatter_flat(bucket, self._group, async_op=True)
+        return dist.all_reduce(bucket, async_op=True)
+
+    def _await_params(self, i: int):
+        """Makes the current stream wait until the parameters of bucket i (-1: the small bucket, else decoder layer i) are
+        updated (overlap_optimizer) and all-gathered (sharded)."""
+        if self._opt_events is not None:
+            torch.cuda.current_stream().wait_event(self._opt_events[0] if i < 0 else self._opt_events[1][i])
+        if self._gathers is not None:
+            w = self._gathers[0] if i < 0 else self._gathers[1][i]
+            if w is not None:
+                w.wait()
 
     @classmethod
     def for_evaluation(cls, model):
@@ -227,9 +325,8 @@ class Stage1Trainer:
         clean/x0_in/t_in: the clean-frame latents and their noise (loss.py:166-192).  Returns the per-frame losses."""
         m, cfg = self.model, self.cfg
         prep = self._prepare(batch)
-        pending = self._opt_events           # the previous step's update may still be running on its own stream
-        if pending is not None:
-            torch.cuda.current_stream().wait_event(pending[0])      # embeddings, heads, final norm: read from the start
+        # the previous step's update may still be running on its own stream, its all-gathers (sharded) still in flight
+        self._await_params(-1)               # embeddings, heads, final norm: read from the start
         B, L, M, H, I = prep["B"], prep["L"], prep["B"] * prep["L"], cfg.hidden_size, cfg.intermediate_size
         nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         nl = cfg.num_hidden_layers
@@ -270,8 +367,7 @@ class Stage1Trainer:
         def layer_forward(li, with_output=True):
             layer = m.llm.layers[li]
             at, mlp, k = layer.self_attn, layer.mlp, sv(li)
-            if pending is not None:
-                torch.cuda.current_stream().wait_event(pending[1][li])   # this layer's parameters are updated
+            self._await_params(li)           # this layer's parameters are updated (and gathered)
             ops.rmsnorm(hbuf[li], layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=n1[k])
             ops.linear_qkv_rope(n1[k], at.qkv_proj.weight, prep["rope"][0], prep["rope"][1], nq, nk, hd, out=qkv[k])
             T.attention_qkv_train(qkv[k].view(B, L, -1), prep["pm"], nq, nk, hd, ctx[k].view(B, L, -1), lse[k])
@@ -379,7 +475,7 @@ class Stage1Trainer:
                           g[f"llm.layers.{li}.input_layernorm.weight"], layer.input_layernorm.variance_epsilon,
                           dres=dh_b)                                                     # dh (layer input)
             if self.world > 1 and not self.skip_allreduce and self.overlap_allreduce:
-                handles.append(dist.all_reduce(self.layer_buckets[li], async_op=True))
+                handles.append(self._reduce(self.layer_buckets[li]))
         # heads fed by dseq = dh
         dseq = dh
         dtt = T.gather_rows(dseq, prep["t_rows"], 1)
@@ -390,10 +486,11 @@ class Stage1Trainer:
         T.embed_bwd(prep["ids"].view(-1), prep["keep"], dseq, g["llm.embed_tokens.weight"])
         if self.world > 1 and not self.skip_allreduce:
             if not self.overlap_allreduce:
-                handles += [dist.all_reduce(b, async_op=True) for b in reversed(self.layer_buckets)]
-            handles.append(dist.all_reduce(self.small_bucket, async_op=True))
+                handles += [self._reduce(b) for b in reversed(self.layer_buckets)]
+            handles.append(self._reduce(self.small_bucket))
             for hd_ in handles:
-                hd_.wait()
+                if hd_ is not None:
+                    hd_.wait()
         if update:
             self.optimizer_step()
         return loss
@@ -434,12 +531,20 @@ class Stage1Trainer:
         self.step_count += 1
         self.sumsq.zero_()
         for b in self.layer_buckets:
-            T.sumsq(b, self.sumsq)
-        T.sumsq(self.small_bucket, self.sumsq)
+            T.sumsq(self._shard(b), self.sumsq)
+        T.sumsq(self._shard(self.small_bucket), self.sumsq)
+        partials = self.sumsq
+        if self._sharded and not self.skip_allreduce:
+            # every rank's sum over its reduced shards, in rank order, added on the device in a fixed order by clip_coef:
+            # every rank computes the same norm and coefficient
+            partials = SPM.all_gather_flat(self.sumsq, self._group, out=self._partials).view(-1)
         w = float(self.world)
         # norm of the AVERAGED gradient = norm(sum)/world; coefficient already carries the 1/world factor
-        T.clip_coef(self.sumsq, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w)
+        T.clip_coef(partials, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w)
         b1, b2 = self.betas
+        if self._sharded:
+            self._sharded_update(lr, b1, b2)
+            return
         if not self.overlap_optimizer:
             for i in range(len(self.layer_buckets)):
                 T.adamw_step(self.master_layers[i], self.param_layers[i], self.layer_buckets[i], self.m_layers[i],
@@ -469,20 +574,63 @@ class Stage1Trainer:
                 evs.append(e)
         self._opt_events = (ev_small, evs)
 
+    def _sharded_update(self, lr, b1, b2):
+        """AdamW on this rank's shard of every bucket, each bucket's bf16 parameters all-gathered in place right behind its
+        update: the small bucket first (embeddings and heads are read first), then the layers in forward order.  With
+        overlap_optimizer on the optimizer's stream behind the clip coefficient with an event per bucket, as in the
+        replicated update; the next forward waits for bucket i's event and gather where it first reads those parameters."""
+        ov = self.overlap_optimizer
+        if ov:
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream())
+            self._opt_stream.wait_event(ready)
+        buckets = [(self.master_small, self.param_small, self.small_bucket, self.m_small, self.v_small)]
+        buckets += list(zip(self.master_layers, self.param_layers, self.layer_buckets, self.m_layers, self.v_layers))
+        evs, works = [], []
+        with torch.cuda.stream(self._opt_stream if ov else torch.cuda.current_stream()):
+            for master, param, grad, m_, v_ in buckets:
+                T.adamw_step(master, self._shard(param), self._shard(grad), m_, v_, lr, b1, b2, self.eps, self.wd,
+                             self.step_count, self.coef)
+                works.append(None if self.skip_allreduce else
+                             SPM.all_gather_flat(self._shard(param), self._group, out=param, async_op=True))
+                if ov:
+                    e = torch.cuda.Event()
+                    e.record(self._opt_stream)
+                    evs.append(e)
+        self._opt_events = (evs[0], evs[1:]) if ov else None
+        self._gathers = (works[0], works[1:])
+
     def finish_optimizer(self):
-        """With overlap_optimizer: makes the current stream wait for the update in flight (call before reading parameters or
-        optimizer state outside step(): checkpoints, evaluation, the end of a timed region)."""
+        """Makes the current stream wait for the update in flight (overlap_optimizer) and for the parameter all-gathers
+        still running (dp_sharding="optimizer"): call before reading parameters or optimizer state outside step()
+        (checkpoints, evaluation, the end of a timed region)."""
         if self._opt_events is not None:
             torch.cuda.current_stream().wait_event(self._opt_events[1][-1])
             self._opt_events = None
+        if self._gathers is not None:
+            for w in [self._gathers[0]] + self._gathers[1]:
+                if w is not None:
+                    w.wait()
+            self._gathers = None
 
 
     # ---- checkpoints (LVM/train/train_x1_stage1_noiseinput.py:304-334,437-451: accelerate's checkpoint-{step}
     #      directories with auto-resume from the highest step).  Written with safetensors, nothing is unpickled on
     #      load: model.safetensors holds the bf16 state_dict under the reference's keys (loadable by
     #      LVM.from_pretrained), optimizer.safetensors the fp32 master weights and Adam moments per bucket. ----
+    def _optimizer_tensors(self):
+        """(tensor of this trainer, optimizer.safetensors key, unpadded bucket length) of every optimizer-state tensor; the
+        tensor is this rank's shard when sharded, else the whole bucket."""
+        pairs = [(self.master_small, "master_small", self._small_numel), (self.m_small, "m_small", self._small_numel),
+                 (self.v_small, "v_small", self._small_numel)]
+        for i, n in enumerate(self._bucket_numel):
+            pairs += [(self.master_layers[i], f"master.{i}", n), (self.m_layers[i], f"m.{i}", n),
+                      (self.v_layers[i], f"v.{i}", n)]
+        return pairs
+
     def save_checkpoint(self, results_dir: str, global_step: Optional[int] = None) -> str:
-        """Rank 0 writes (replicas are identical under data parallelism); every rank returns after the files exist."""
+        """Rank 0 writes (replicas are identical under data parallelism; a sharded optimizer state is gathered to it one
+        bucket at a time through host memory, in the replicated layout); every rank returns after the files exist."""
         self.finish_optimizer()
         import json
         import os
@@ -490,14 +638,21 @@ class Stage1Trainer:
         step = self.step_count if global_step is None else int(global_step)
         path = os.path.join(results_dir, f"checkpoint-{step}")
         distributed = dist.is_available() and dist.is_initialized()
-        if not distributed or dist.get_rank() == 0:
+        writer = not distributed or dist.get_rank() == 0
+        opt = {}
+        for t, key, n in self._optimizer_tensors():
+            if self._sharded:     # every rank takes part; one gathered bucket on the device at a time, then host memory
+                full = SPM.all_gather_flat(t, self._group).view(-1)[:n]
+                if writer:
+                    opt[key] = full.cpu()
+                del full
+            elif writer:
+                opt[key] = t.detach().cpu().contiguous()
+        if writer:
             os.makedirs(path, exist_ok=True)
             save_file({k: v.detach().cpu().contiguous() for k, v in self.model.state_dict().items()},
                       os.path.join(path, "model.safetensors"))
-            opt = {"master_small": self.master_small, "m_small": self.m_small, "v_small": self.v_small}
-            for i in range(len(self.master_layers)):
-                opt[f"master.{i}"], opt[f"m.{i}"], opt[f"v.{i}"] = self.master_layers[i], self.m_layers[i], self.v_layers[i]
-            save_file({k: v.detach().cpu().contiguous() for k, v in opt.items()}, os.path.join(path, "optimizer.safetensors"))
+            save_file(opt, os.path.join(path, "optimizer.safetensors"))
             with open(os.path.join(path, "trainer_state.json"), "w") as f:
                 json.dump({"step_count": self.step_count, "global_step": step, "lr": self.lr, "weight_decay": self.wd,
                            "betas": list(self.betas), "eps": self.eps, "lr_scheduler": self.lr_scheduler,
@@ -509,7 +664,8 @@ class Stage1Trainer:
     def load_checkpoint(self, path: str, restore_hyperparameters: bool = True) -> int:
         """Restores parameters, fp32 master weights, Adam moments, the step counter and (by default) the optimizer
         hyper-parameters and LR schedule; returns the global step.  Everything is validated before anything is copied.
-        Only checkpoints written by this trainer resume (the reference's are accelerate / DeepSpeed `save_state`
+        The optimizer state is stored unpadded and unsharded: a sharded trainer copies its own slice, so checkpoints move
+        between dp_sharding modes and world sizes.  Only checkpoints written by this trainer resume (the reference's are accelerate / DeepSpeed `save_state`
         directories, whose optimizer shards are pickles: warm-start from those through LVM.from_pretrained's weight
         loaders instead)."""
         self.finish_optimizer()
@@ -521,21 +677,26 @@ class Stage1Trainer:
         if st["small_names"] != self.small_names:
             raise VgptError("checkpoint was written for a different parameter layout")
         opt = load_file(os.path.join(path, "optimizer.safetensors"))
-        pairs = [(self.master_small, "master_small"), (self.m_small, "m_small"), (self.v_small, "v_small")]
-        for i in range(len(self.master_layers)):
-            pairs += [(self.master_layers[i], f"master.{i}"), (self.m_layers[i], f"m.{i}"), (self.v_layers[i], f"v.{i}")]
+        pairs = self._optimizer_tensors()
         model_sd = load_file(os.path.join(path, "model.safetensors"))
         own = self.model.state_dict()
-        problems = [f"optimizer tensor {k} missing" for _, k in pairs if k not in opt]
-        problems += [f"optimizer tensor {k}: shape {tuple(opt[k].shape)} != {tuple(d.shape)}" for d, k in pairs
-                     if k in opt and opt[k].shape != d.shape]
+        problems = [f"optimizer tensor {k} missing" for _, k, _ in pairs if k not in opt]
+        problems += [f"optimizer tensor {k}: shape {tuple(opt[k].shape)} != {(n,)}" for _, k, n in pairs
+                     if k in opt and tuple(opt[k].shape) != (n,)]
         problems += [f"model tensor {k} missing" for k in own if k not in model_sd]
         problems += [f"model tensor {k}: shape {tuple(model_sd[k].shape)} != {tuple(v.shape)}" for k, v in own.items()
                      if k in model_sd and model_sd[k].shape != v.shape]
         if problems:
             raise VgptError(f"{path}: checkpoint does not match this trainer: " + "; ".join(problems[:8]))
-        for dst, key in pairs:
-            dst.copy_(opt[key])
+        for dst, key, _ in pairs:
+            if not self._sharded:
+                dst.copy_(opt[key])
+                continue
+            lo = self.rank * dst.numel()                 # this rank's slice; the zero padding past the bucket stays zero
+            hi = min(lo + dst.numel(), opt[key].numel())
+            dst.zero_()
+            if hi > lo:
+                dst[:hi - lo].copy_(opt[key][lo:hi])
         with torch.no_grad():     # parameters are views of the flat bf16 buffers: copy in place, keep the views
             for k, p_ in own.items():
                 p_.copy_(model_sd[k])
