@@ -179,7 +179,7 @@ def test_attention_backward(ops, T, B, L, nh, nkv):
     T.attention_qkv_train(qd, pm, nh, nkv, hd, out, lse)
     assert rel_l2(out, o) < 1e-2
     lse_ref = torch.logsumexp(s, -1) / math.log(2)
-    assert float((lse.cpu() - lse_ref.float()).abs().max()) < 2e-2
+    assert float((lse.cpu() - lse_ref.float()).abs().max()) < 1e-4   # measured <= 4.2e-6 (test_train_kernels_gpu.py)
     dqkv = torch.empty(B, L, width, dtype=BF, device=DEV)
     delta = torch.empty(B, nh, L, dtype=torch.float32, device=DEV)
     T.attention_qkv_bwd(qd, out, dout.to(DEV, BF), lse, delta, dqkv, pm, nh, nkv, hd)

@@ -890,7 +890,10 @@ VGPT_EXPORT int vgpt_adamw_step(float* master, void* param, const void* grad, in
     VGPT_REQUIRE(master && param && grad && m && v, VGPT_ERR_INVALID, "vgpt_adamw_step: null pointer");
     VGPT_REQUIRE(n >= 0 && step >= 1, VGPT_ERR_INVALID, "vgpt_adamw_step: bad argument");
     if (n == 0) return VGPT_OK;
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+    // in double, as torch.optim.AdamW does: 1 - beta2^step cancels at small steps (1 - powf(0.999f, 2) in fp32 is 6.7e-6
+    // off, relative), and that error went straight into every update of the first steps
+    const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step)),
+                bc2 = (float)(1.0 - std::pow((double)beta2, (double)step));
     VGPT_REQUIRE(((((uintptr_t)master | (uintptr_t)m | (uintptr_t)v) & 15) == 0) && (((uintptr_t)param | (uintptr_t)grad) & 7) == 0 &&
                      (!grad_f32 || ((uintptr_t)grad & 15) == 0),
                  VGPT_ERR_UNSUPPORTED, "vgpt_adamw_step: buffers must be 16-byte (fp32) / 8-byte (bf16) aligned");
