@@ -631,21 +631,50 @@ __global__ void conv_pack_b1_kernel(const float* __restrict__ w, char* __restric
 }
 
 // ---- GroupNorm statistics: one 1024-thread block per (n, group), ONE pass over the group ----
-// Sums of d = x - K and d^2 with the shift K = the group's first element (close to the mean, so Q/n - (S/n)^2 does
-// not cancel), four independent 16-byte loads per thread and iteration; per-thread partial sums, then a wave / LDS
-// tree.  (The two-pass version read every group twice with scalar loads: 2 TB/s, a quarter of the VAE's time.)
+// Sums of d = x - K and d^2 with a shift K close to the mean, so that Q/n - (S/n)^2 does not cancel; four independent
+// 16-byte loads per thread and iteration; per-thread partial sums, then a wave / LDS tree.  K is the mean of the block's
+// FIRST LOADS (the group's first min(n, 4096) elements, 1024 on the scalar path): every thread keeps its first load in
+// registers across the small reduction that gives K and accumulates it afterwards, so the group is still read once.
+// (K was the group's first element -- the top-left corner pixel of a channel -- until an outlier there was measured to
+// leave rstd two digits: 1.5e-2 off at n = 262144 with the first element 1000 std away, Q/n - (S/n)^2 then being the
+// difference of two numbers 10^6 times its size (tests/test_vae_kernels_gpu.py).  One outlier now moves K by 1/4096 of
+// itself.  The two-pass version read every group twice with scalar loads: 2 TB/s, a quarter of the VAE's time.)
 __global__ __launch_bounds__(1024) void gn_stats_kernel(const float* __restrict__ x, float* __restrict__ stats,
                                                         int64_t group_elems, float eps) {
-    __shared__ float red[2][16];
+    __shared__ float red[3][16];
     const float* p = x + (int64_t)blockIdx.x * group_elems;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float K = p[0];
-    float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
     const bool vec = (group_elems & 3) == 0 && (((uintptr_t)p) & 15) == 0;
+    const int64_t n4 = group_elems >> 2;
+    const f32x4* p4 = reinterpret_cast<const f32x4*>(p);
+    // first load of every thread (zeros past the end) and the shift K = mean of these elements
+    f32x4 v0 = f32x4{0.f, 0.f, 0.f, 0.f};
+    int64_t n0;   // how many elements the first loads cover
     if (vec) {
-        const int64_t n4 = group_elems >> 2;
-        const f32x4* p4 = reinterpret_cast<const f32x4*>(p);
-        int64_t i = threadIdx.x;
+        if (threadIdx.x < n4) v0 = p4[threadIdx.x];
+        n0 = 4 * (n4 < 1024 ? n4 : 1024);
+    } else {
+        if (threadIdx.x < group_elems) v0[0] = p[threadIdx.x];
+        n0 = group_elems < 1024 ? group_elems : 1024;
+    }
+    const float kw = wave_sum((v0[0] + v0[1]) + (v0[2] + v0[3]));
+    if (lane == 0) red[2][wave] = kw;
+    __syncthreads();
+    float K = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) K += red[2][w];
+    K /= (float)n0;
+    float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+    if (vec) {
+        if (threadIdx.x < n4) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float d = v0[j] - K;
+                s[3] += d;
+                q[3] += d * d;
+            }
+        }
+        int64_t i = threadIdx.x + 1024;
         for (; i + 3 * 1024 < n4; i += 4 * 1024) {
             f32x4 v[4];
 #pragma unroll
@@ -669,7 +698,12 @@ __global__ __launch_bounds__(1024) void gn_stats_kernel(const float* __restrict_
             }
         }
     } else {
-        for (int64_t i = threadIdx.x; i < group_elems; i += 1024) {
+        if (threadIdx.x < group_elems) {
+            const float d = v0[0] - K;
+            s[0] = d;
+            q[0] = d * d;
+        }
+        for (int64_t i = (int64_t)threadIdx.x + 1024; i < group_elems; i += 1024) {
             const float d = p[i] - K;
             s[0] += d;
             q[0] += d * d;
