@@ -13,9 +13,10 @@ identical for every step.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
-
+import os
 import weakref
+from types import SimpleNamespace
+from typing import Dict, List, Optional
 
 import torch
 
@@ -158,7 +159,7 @@ class StaticDenoiser:
         self.lin_fp8 = linear_precision == "fp8"
         # sequence_parallel: under a sequence-parallel group of P > 1 ranks (sequence_parallel.py) every rank holds about 1/P
         # of the live rows and 1/P of the attention heads (Ulysses, LVM/model.py:457-474 + LVM/transform/sdpa_transform.py:
-        # 94-159); see _sp_plan.  Off, or with one rank: the replicated engine, unchanged.
+        # 94-159); see the block comment at _sp_plan.  Off, or with one rank: the replicated engine, unchanged.
         from . import sequence_parallel as SPM
         self.sp = None
         if sequence_parallel and SPM.sp_world(sp_group) > 1:
@@ -173,7 +174,6 @@ class StaticDenoiser:
         # L2 -> LDS bytes per FLOP; head dim 96): bit-identical results, measured SLOWER in round 3 -- 159.5 / 160.4 us per
         # layer against 148.3 us at the cfg-2 live rows, same box (a barrier across eight waves per tile costs more than the
         # staging it saves) -- and kept behind VGPT_ATTN_ITEM_ROWS=256 for A/B runs.
-        import os
         self.attn_item_rows = int(os.environ.get("VGPT_ATTN_ITEM_ROWS", "128"))
         self.model = model
         cfg = model.llm.config
@@ -318,9 +318,10 @@ class StaticDenoiser:
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
         self.sigma = None
         if sigma is not None:
-            self.set_sigma(sigma)
+            self.sigma = sigma.to(dev, torch.float32).contiguous()
+            self.num_steps = self.sigma.numel() - 1
         # workspaces
-        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        self.heads = nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         if self.sp is not None:
             if B != 1:
                 raise VgptError("StaticDenoiser: sequence_parallel needs one packed sequence (a batch of one, or left-padded "
@@ -383,38 +384,119 @@ class StaticDenoiser:
             else:
                 self.prefill()
 
+    # ---- pieces every pass shares ---------------------------------------------------------------------------------------
+    def _embed_cond(self, seq2d):
+        """The condition frames' patch embeddings into their rows of seq2d (rows, H)."""
+        m = self.model
+        if self.cond is not None:
+            ops.patch_embed(self.cond, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, m.pos_embed[0],
+                            self.cond_rows, seq2d, m.pos_embed_max_size)
+
+    def _embed_static(self, hid, n: int):
+        """Rows [0, n) of hid (1, >= n, H), all inside the static prefix: token embeddings + the condition frames' patches."""
+        ops.embed_gather(self.input_ids[:, :n].contiguous(), self.model.llm.embed_tokens.weight, out=hid[:, :n])
+        self._embed_cond(hid.view(-1, self.H))
+
+    def _sigma_mlp(self, emb, sin, outs, tail=None):
+        """sigma_0 .. sigma_{T-1}, one row per step (every frame of a step carries the same t, LVM/scheduler.py:169), through
+        the timestep embedder `emb`: sinusoid into `sin`, Linear + SiLU into outs[0], Linear into outs[1] and, with `tail`,
+        SiLU + that Linear into outs[2].  Same small-M kernels as the per-step path, at most 32 rows per call."""
+        T = self.num_steps
+        ops.timestep_sinusoid(self.sigma[:T].contiguous(), emb.freqs(self.dev), out=sin)
+        chain = [(emb.mlp[0], {"post_act": ops.ACT_SILU}), (emb.mlp[2], {})]
+        if tail is not None:
+            chain.append((tail, {"pre_act": ops.ACT_SILU}))
+        for c in range(0, T, 32):
+            src = sin
+            for (lin, kw), dst in zip(chain, outs):
+                ops.linear_small(src[c:c + 32], lin.weight, lin.bias, out=dst[c:c + 32], **kw)
+                src = dst
+
+    def _pass_workspaces(self, M: int):
+        """Workspaces of a per-clip pass over M rows: `hid` for every row (the sequence assembly runs on all of them), nrm /
+        ctx / act for the rows [a, b) its decoder layers run on -- all M, or this rank's share with the exchange buffers."""
+        nq, _, hd = self.heads
+        e = lambda *s_: torch.empty(*s_, dtype=BF16, device=self.dev)
+        shares, (a, b) = None, (0, M)
+        if self.sp is not None:
+            shares, _ = sp_shares(M, self.sp["P"])
+            a, b = shares[self.sp["r"]]
+        ws = SimpleNamespace(shares=shares, a=a, b=b, hid=e(1, M, self.H), nrm=e(1, b - a, self.H), ctx=e(1, b - a, nq * hd),
+                             act=e(1, b - a, self.cfg.intermediate_size))
+        ws.bufs = self._sp_buffers(M, b - a) if self.sp is not None else None
+        return ws
+
+    def _layers(self, hid, nrm, ctx, act, rope, qkv_dst, attention, fz=None, mx=None):
+        """The decoder layers over the residual rows `hid` (1, rows, H), in place -- all rows of a pass, or one rank's share:
+        norm -> qkv + RoPE -> attention -> o_proj + residual -> norm -> gate_up + act * up -> down + residual.
+        nrm / ctx / act: workspaces of the same rows; rope: their (cos, sin) rows.  qkv_dst(li): where layer li's q/k/v rows
+        go; attention(li): everything between that GEMM and o_proj, leaving the rows' attention output in `ctx` -- direct on
+        the fused buffer, or through the exchanges (_sp_attention).  Projection form: separate RMSNorm kernels on the live
+        parameters (the per-clip passes, always); fz (self.fuse): both norms folded into the GEMMs around them; mx
+        (self.mx8): the MX-fp8 projections, which fold the norms themselves."""
+        layers = self.model.llm.layers
+        nq, nk, hd = self.heads
+        if fz is not None:
+            # the statistics of the first norm: the embedded rows are no GEMM's output.  From here on every residual stream is
+            # written by linear_resid_rstd, which leaves the next norm's 1 / rms behind
+            ops.rms_rstd(hid, layers[0].input_layernorm.variance_epsilon, out=fz["rstd_in"])
+        for li, layer in enumerate(layers):
+            at, mlp, ln_in, ln_post = layer.self_attn, layer.mlp, layer.input_layernorm, layer.post_attention_layernorm
+            if mx is not None:
+                w = mx["w"][li]
+                ops.mx8_quantize_rows(hid, mx["a_hid"], mx["rstd"], ln_in.variance_epsilon)
+                ops.linear_mx8(mx["a_hid"], w["qkv"], qkv_dst(li), "rope", rstd=mx["rstd"], cos=rope[0], sin=rope[1],
+                               n_rot_heads=nq + nk, head_dim=hd)
+            elif fz is not None:
+                ops.linear_qkv_rope_prenorm(hid, fz["wq"][li], rope[0], rope[1], fz["rstd_in"], nq, nk, hd, out=qkv_dst(li))
+            else:
+                ops.rmsnorm(hid, ln_in.weight, ln_in.variance_epsilon, out=nrm)
+                ops.linear_qkv_rope(nrm, at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=qkv_dst(li))
+            attention(li)
+            if mx is not None:
+                ops.mx8_quantize_rows(ctx, mx["a_ctx"])
+                ops.linear_mx8(mx["a_ctx"], w["o"], hid, "resid", residual=hid)
+                ops.mx8_quantize_rows(hid, mx["a_hid"], mx["rstd"], ln_post.variance_epsilon)
+                ops.linear_mx8(mx["a_hid"], w["gate_up"], act, "gated", rstd=mx["rstd"], act=mlp.act)
+                ops.mx8_quantize_rows(act, mx["a_act"])
+                ops.linear_mx8(mx["a_act"], w["down"], hid, "resid", residual=hid)
+            elif fz is not None:
+                ops.linear_resid_rstd(ctx, at.o_proj.weight, hid, fz["rstd_post"], fz["ws"], ln_post.variance_epsilon, out=hid)
+                ops.gated_mlp_act_prenorm(hid, fz["wgu"][li], fz["rstd_post"], mlp.act, out=act)
+                # the statistic the NEXT layer's input norm reads (its eps; the last layer's goes unused: the final norm is a
+                # separate kernel)
+                nxt = layers[min(li + 1, len(layers) - 1)].input_layernorm.variance_epsilon
+                ops.linear_resid_rstd(act, mlp.down_proj.weight, hid, fz["rstd_in"], fz["ws"], nxt, out=hid)
+            else:
+                ops.linear(ctx, at.o_proj.weight, residual=hid, out=hid)
+                ops.rmsnorm(hid, ln_post.weight, ln_post.variance_epsilon, out=nrm)
+                ops.gated_mlp_act(nrm, mlp.gate_up_proj.weight, mlp.act, out=act)
+                ops.linear(act, mlp.down_proj.weight, residual=hid, out=hid)
+
+    # ---- the per-clip passes --------------------------------------------------------------------------------------------
     def prefill(self):
         """One forward over the static prefix rows [0, S) ONLY -- they never see a later row (that is what makes them
         step-invariant), so nothing else is needed to produce them -- leaving every layer's (post-RoPE) q/k/v in
         qkv_full[l][:S].  Rows >= S of qkv_full are written by every step (zero until the first one: the buffer is
-        zero-initialised so that masked keys are finite)."""
-        if self.sp is not None:
-            return self._sp_prefill()
-        m, cfg, H = self.model, self.cfg, self.H
+        zero-initialised so that masked keys are finite).  Sharded: the rows are cut into shares."""
+        nq, nk, hd = self.heads
         # with hoisting the step-invariant `<|diffusion|>` rows (right behind the prefix) are computed here as well: they
         # see the prefix and each other, nothing else
         S = self.S0 + (self.hoist["nf"] if self.hoist else 0)
-        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        e = lambda *s: torch.empty(*s, dtype=BF16, device=self.dev)
-        hid, nrm, ctx, act = e(1, S, H), e(1, S, H), e(1, S, nq * hd), e(1, S, cfg.intermediate_size)
-        ops.embed_gather(self.input_ids[:, :S].contiguous(), m.llm.embed_tokens.weight, out=hid)
-        if self.cond is not None:
-            ops.patch_embed(self.cond, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, m.pos_embed[0],
-                            self.cond_rows, hid.view(-1, H), m.pos_embed_max_size)
-        rope = (self.rope[0][:S].contiguous(), self.rope[1][:S].contiguous())
+        ws = self._pass_workspaces(S)
+        self._embed_static(ws.hid, S)
         seg = ((0, 0, S),)   # includes the pad rows S0..S: no visible key -> zeros, which keeps their K/V finite
-        for li, layer in enumerate(m.llm.layers):
-            at, mlp = layer.self_attn, layer.mlp
-            full = self.qkv_full[li]
-            ops.rmsnorm(hid, layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=nrm)
-            ops.linear_qkv_rope(nrm, at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=full[:S])
-            if self.attn_fp8:   # the sampler steps read the prefix's K / V from the fp8 workspace of this layer
-                ops.attention_fp8_quantize(full.view(1, self.L, -1), self.fp8_ws[li], nq, nk, hd)
-            ops.attention_qkv_range(full.view(1, self.L, -1), self.pm, nq, nk, hd, 0, ctx, segments=seg)
-            ops.linear(ctx, at.o_proj.weight, residual=hid, out=hid)
-            ops.rmsnorm(hid, layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon, out=nrm)
-            ops.gated_mlp_act(nrm, mlp.gate_up_proj.weight, mlp.act, out=act)
-            ops.linear(act, mlp.down_proj.weight, residual=hid, out=hid)
+        if self.sp is None:
+            def attention(li):
+                full = self.qkv_full[li].view(1, self.L, -1)
+                if self.attn_fp8:   # the sampler steps read the prefix's K / V from the fp8 workspace of this layer
+                    ops.attention_fp8_quantize(full, self.fp8_ws[li], nq, nk, hd)
+                ops.attention_qkv_range(full, self.pm, nq, nk, hd, 0, ws.ctx, segments=seg)
+            qkv_dst = lambda li: self.qkv_full[li][:S]
+        else:
+            qkv_dst, attention = self._sp_attention(ws.bufs, ws.shares, lambda li: self.qkv_full[li], 0, self.pm, seg, ws.ctx)
+        rope = tuple(t_[ws.a:ws.b].contiguous() for t_ in self.rope)
+        self._layers(ws.hid[:, ws.a:ws.b], ws.nrm, ws.ctx, ws.act, rope, qkv_dst, attention)
         torch.cuda.current_stream().synchronize()
 
     def rebind(self, input_img_latents):
@@ -473,26 +555,21 @@ class StaticDenoiser:
             ops.mx8_quantize_weight(mlp.down_proj.weight, out=w["down"])
 
     def set_sigma(self, sigma: torch.Tensor):
+        """A new sigma table on a built engine: everything that depends on the step index alone is recomputed."""
         self.sigma = sigma.to(self.dev, torch.float32).contiguous()
         self.num_steps = self.sigma.numel() - 1
-        if getattr(self, "mod", None) is not None:
-            self._mod_pass()
-        if getattr(self, "hoist", None) and getattr(self, "qkv_full", None) is not None:
+        self._mod_pass()
+        if self.hoist:
             self._clip_pass()
 
     def _mod_pass(self):
         """t_embedder MLP + adaLN modulation of the final layer for EVERY step in one pass per clip: they depend on
         sigma_i alone (every frame of a step carries the same t, LVM/scheduler.py:169), while the reference recomputes
         them inside every model call (LVM/model.py:480-486).  A step then copies its row (step index read on the device)."""
-        m, dev, H, T = self.model, self.dev, self.H, self.num_steps
-        e = lambda *s_: torch.empty(*s_, dtype=BF16, device=dev)
+        m, H, T = self.model, self.H, self.num_steps
+        e = lambda *s_: torch.empty(*s_, dtype=BF16, device=self.dev)
         sin, te_h, temb, mod = e(T, 256), e(T, H), e(T, H), e(T, 2 * H)
-        ops.timestep_sinusoid(self.sigma[:T].contiguous(), m.t_embedder.freqs(dev), out=sin)
-        te, ada = m.t_embedder.mlp, m.final_layer.adaLN_modulation[1]
-        for c in range(0, T, 32):   # the small-M kernel takes at most 32 rows per call
-            ops.linear_small(sin[c:c + 32], te[0].weight, te[0].bias, post_act=ops.ACT_SILU, out=te_h[c:c + 32])
-            ops.linear_small(te_h[c:c + 32], te[2].weight, te[2].bias, out=temb[c:c + 32])
-            ops.linear_small(temb[c:c + 32], ada.weight, ada.bias, pre_act=ops.ACT_SILU, out=mod[c:c + 32])
+        self._sigma_mlp(m.t_embedder, sin, (te_h, temb, mod), tail=m.final_layer.adaLN_modulation[1])
         shape = (T, 1, self.nf, 2 * H)
         if self.mod_all is None or tuple(self.mod_all.shape) != shape:
             self.mod_all = e(*shape)          # a captured graph reads this buffer: re-allocating invalidates it
@@ -534,80 +611,75 @@ class StaticDenoiser:
                 f0 = f
         return dict(perm=perm, inv=inv, S=S, nf=nf, ntok=ntok, segments=tuple(segs))
 
+    def _clip_layout(self):
+        """Mask and row counts of the per-clip pass of a hoisted layout (_clip_pass): pm, Sc (the rows the sampler steps read
+        from the cache: prefix + `<|diffusion|>` rows), Lp (all rows of the pass).  The time rows of step s carry sub-group
+        s + 1 (layout.TokenLayout): they see the prefix, their clip's `<|diffusion|>` columns (sub-group 0) and the time
+        columns of their own step only."""
+        import numpy as np
+        nf, T = self.hoist["nf"], self.num_steps
+        Sc = self.S0 + nf
+        idx = np.concatenate([np.arange(Sc), np.tile(np.arange(Sc, Sc + nf), T)])
+        lp = self.layout.permute(idx)
+        sub = lp.sub.copy()
+        sub[0, Sc:] = 1 + np.repeat(np.arange(T), nf)
+        return lp.with_subgroups(sub).packed_mask(self.dev), Sc, Sc + T * nf
+
     def _clip_pass(self):
         """Everything of a hoisted clip that does not depend on the latents, in ONE forward per clip: the condition prefix
         and the `<|diffusion|>` rows (step-invariant; what prefill() computes) and the time rows of EVERY denoise step (a
         function of the step index alone).  The reference recomputes all of them inside every model call
         (LVM/model.py:435-454, LVM/scheduler.py:174).  Sequence of the pass:
             [prefix 0..S0) | nf `<|diffusion|>` rows | step 0's nf time rows | step 1's | ... | step T-1's]
-        with the clip's own token attributes, the time rows of step s carrying sub-group s + 1 (layout.TokenLayout): they
-        see the prefix, their clip's `<|diffusion|>` columns (sub-group 0) and the time columns of their own step only.
-        One sequence means every layer's weights stream once per clip and the GEMMs run S0 + nf + T nf rows (1.9 k at
-        cfg-2 with 53 steps) instead of two passes of about half that.  Leaves qkv_full[l][:S0 + nf] (post-RoPE q/k/v of
-        the cached rows) and time_qkv[step, l]."""
-        if self.sp is not None:
-            return self._sp_clip_pass()
-        import numpy as np
-        m, cfg, H, dev = self.model, self.cfg, self.H, self.dev
-        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        W3 = (nq + 2 * nk) * hd
-        S0, nf, T = self.S0, self.hoist["nf"], self.num_steps
-        Sc = S0 + nf                                       # rows the sampler steps read from the cache
-        Lp = Sc + T * nf
-        idx = np.concatenate([np.arange(Sc), np.tile(np.arange(Sc, Sc + nf), T)])
-        lp = self.layout.permute(idx)
-        sub = lp.sub.copy()
-        sub[0, Sc:] = 1 + np.repeat(np.arange(T), nf)
-        pm = lp.with_subgroups(sub).packed_mask(dev)
-        e = lambda *s_, dt=BF16: torch.empty(*s_, dtype=dt, device=dev)
-        hid, nrm, ctx, act = e(1, Lp, H), e(1, Lp, H), e(1, Lp, nq * hd), e(1, Lp, cfg.intermediate_size)
-        # rows [0, Sc): token embeddings + the condition frames' patch embeddings, as prefill()
-        ops.embed_gather(self.input_ids[:, :Sc].contiguous(), m.llm.embed_tokens.weight, out=hid[:, :Sc])
-        if self.cond is not None:
-            ops.patch_embed(self.cond, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, m.pos_embed[0],
-                            self.cond_rows, hid.view(-1, H), m.pos_embed_max_size)
-        # time_token(sigma_s): one value per step (every frame of a step carries the same t, LVM/scheduler.py:169),
-        # through the same small-M kernels as the per-step path (at most 32 rows per call), then broadcast to the rows
-        ts = self.sigma[:T].contiguous()
+        with the clip's own token attributes (_clip_layout).  One sequence means every layer's weights stream once per clip
+        and the GEMMs run S0 + nf + T nf rows (1.9 k at cfg-2 with 53 steps) instead of two passes of about half that.
+        Leaves qkv_full[l][:S0 + nf] (post-RoPE q/k/v of the cached rows) and time_qkv[step, l]; sharded, the pass's rows
+        are cut into shares and every rank keeps both for its own heads."""
+        m, H = self.model, self.H
+        nq, nk, hd = self.heads
+        nf, T = self.hoist["nf"], self.num_steps
+        pm, Sc, Lp = self._clip_layout()
+        W = self.qkv_full.shape[-1]                        # q/k/v of all heads, or of this rank's
+        e = lambda *s_: torch.empty(*s_, dtype=BF16, device=self.dev)
+        ws = self._pass_workspaces(Lp)
+        self._embed_static(ws.hid, Sc)                     # rows [0, Sc) as prefill()
+        # time_token(sigma_s): one value per step, broadcast to the step's rows
         sin, tt_h, tt_o = e(T, 256), e(T, H), e(T, H)
-        ops.timestep_sinusoid(ts, m.time_token.freqs(dev), out=sin)
-        tt = m.time_token.mlp
-        for c in range(0, T, 32):
-            ops.linear_small(sin[c:c + 32], tt[0].weight, tt[0].bias, post_act=ops.ACT_SILU, out=tt_h[c:c + 32])
-            ops.linear_small(tt_h[c:c + 32], tt[2].weight, tt[2].bias, out=tt_o[c:c + 32])
-        hid[0, Sc:].view(T, nf, H)[:] = tt_o[:, None, :]
+        self._sigma_mlp(m.time_token, sin, (tt_h, tt_o))
+        ws.hid[0, Sc:].view(T, nf, H)[:] = tt_o[:, None, :]
         # cos / sin are ROWS OF THE CLIP'S OWN TABLE (self.rope, built from the full position_ids): a su / longrope
         # checkpoint picks short or long factors from the largest position of the WHOLE sequence (HF 4.47.1
         # Phi3LongRoPEScaledRotaryEmbedding), which a table rebuilt from this pass's rows alone would get wrong whenever
         # only the image rows cross original_max_position_embeddings
-        rope = tuple(torch.cat([t_[:Sc], t_[Sc:Sc + nf].repeat(T, 1)]).contiguous() for t_ in self.rope)
-        buf = e(1, Lp, W3)
-        shape = (T, cfg.num_hidden_layers, nf, W3)
+        rope = tuple(torch.cat([t_[:Sc], t_[Sc:Sc + nf].repeat(T, 1)])[ws.a:ws.b].contiguous() for t_ in self.rope)
+        buf = e(Lp, W)                                     # the pass's fused q/k/v rows, one layer at a time
+        shape = (T, self.cfg.num_hidden_layers, nf, W)
         if self.time_qkv is None or tuple(self.time_qkv.shape) != shape:
             self.time_qkv = e(*shape)      # a captured graph reads this buffer: re-allocating invalidates it
             self.graph = None
         seg = ((0, 0, Lp),)
-        for li, layer in enumerate(m.llm.layers):
-            at, mlp = layer.self_attn, layer.mlp
-            full = self.qkv_full[li]
-            ops.rmsnorm(hid, layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=nrm)
-            ops.linear_qkv_rope(nrm, at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=buf)
-            full[:Sc].copy_(buf[0, :Sc])
-            self.time_qkv[:, li].copy_(buf[0, Sc:].view(T, nf, W3))
-            if self.attn_fp8:   # the sampler steps read the cached rows' K / V from the fp8 workspace of this layer
-                ops.attention_fp8_quantize(full.view(1, self.L, -1), self.fp8_ws[li], nq, nk, hd)
-            ops.attention_qkv_range(buf, pm, nq, nk, hd, 0, ctx, segments=seg)
-            ops.linear(ctx, at.o_proj.weight, residual=hid, out=hid)
-            ops.rmsnorm(hid, layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon, out=nrm)
-            ops.gated_mlp_act(nrm, mlp.gate_up_proj.weight, mlp.act, out=act)
-            ops.linear(act, mlp.down_proj.weight, residual=hid, out=hid)
+
+        def keep(li):
+            self.qkv_full[li][:Sc].copy_(buf[:Sc])
+            self.time_qkv[:, li].copy_(buf[Sc:].view(T, nf, W))
+        if self.sp is None:
+            def attention(li):
+                keep(li)
+                if self.attn_fp8:   # the sampler steps read the cached rows' K / V from the fp8 workspace of this layer
+                    ops.attention_fp8_quantize(self.qkv_full[li].view(1, self.L, -1), self.fp8_ws[li], nq, nk, hd)
+                ops.attention_qkv_range(buf.view(1, Lp, W), pm, nq, nk, hd, 0, ws.ctx, segments=seg)
+            qkv_dst = lambda li: buf
+        else:   # buf collects the rows of every rank for this rank's heads
+            qkv_dst, attention = self._sp_attention(ws.bufs, ws.shares, lambda li: buf, 0, pm, seg, ws.ctx, keep=keep)
+        self._layers(ws.hid[:, ws.a:ws.b], ws.nrm, ws.ctx, ws.act, rope, qkv_dst, attention)
         self.time_dst = self.qkv_full[:, Sc:Sc + nf]    # (layers, nf, 3H) view the step copy writes
         torch.cuda.current_stream().synchronize()
 
     # ---- Ulysses sequence parallelism (sequence_parallel=True under a group of P > 1 ranks) ---------------------------
     # Every pass (a step, prefill, the per-clip pass) cuts its live rows into P contiguous shares (sp_shares); rank r runs
     # the row-local work of its share -- RMSNorm (or the folded form), qkv_proj + RoPE, o_proj + residual, gate_up + act*up,
-    # down + residual -- and the attention of its nq/P query heads (nk/P K/V heads) over ALL rows.  Per layer:
+    # down + residual: _layers on the share -- and the attention of its nq/P query heads (nk/P K/V heads) over ALL rows
+    # (_sp_attention).  Per layer:
     #   qkv rows of the share -> sp_pack_qkv -> one all-to-all -> rows of every rank for my heads, straight into the
     #   layer's fused buffer of width (nq/P + 2 nk/P) hd behind the cached rows -> attention -> ctx rows cut by owner ->
     #   second all-to-all -> sp_unpack_ctx -> (share, nq hd) in head order, the operand o_proj reads at P = 1.
@@ -620,7 +692,7 @@ class StaticDenoiser:
         """Buffers of the sharded per-step forward (B == 1)."""
         cfg, H, dev, sp = self.cfg, self.H, self.dev, self.sp
         P, r = sp["P"], sp["r"]
-        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        nq, nk, hd = self.heads
         if nq % P or nk % P:
             raise VgptError(f"StaticDenoiser: sequence_parallel over {P} ranks needs num_attention_heads ({nq}) and "
                             f"num_key_value_heads ({nk}) divisible by {P}")
@@ -640,8 +712,6 @@ class StaticDenoiser:
         # by every layer before it is read, so one buffer serves all layers
         self.qkv_full = torch.zeros(cfg.num_hidden_layers if S else 1, L, Wl, dtype=BF16, device=dev)
         self.sp_bufs = self._sp_buffers(Ml, m)
-        rope = self.rope_a if S else self.rope
-        self.sp_rope = (rope[0][a:b].contiguous(), rope[1][a:b].contiguous())
         # the final layer: frames with a row in this share, and for every element of pred the rank that computed it
         x_rows = [int(v) for v in (self.x_rows_a if S else self.x_rows).tolist()]
         ntok = (self.h // 2) * (self.w // 2)
@@ -656,187 +726,35 @@ class StaticDenoiser:
         self.pred_loc = torch.zeros_like(self.pred)
 
     def _sp_buffers(self, Mtot: int, m: int):
-        cfg, P = self.cfg, self.sp["P"]
-        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        """Exchange buffers of a sharded pass over Mtot rows of which this rank runs m."""
+        nq, nk, hd = self.heads
+        P = self.sp["P"]
         e = lambda *s_: torch.empty(*s_, dtype=BF16, device=self.dev)
         return {"qkv": e(m, (nq + 2 * nk) * hd), "send": e(P, m, self.sp["Wl"]), "ctx_all": e(Mtot, nq // P * hd),
                 "ctx_recv": e(P, m, nq // P * hd)}
 
-    def _sp_attention(self, bufs, shares, full, q0: int, pm, segments, ctx_out, item_rows=None):
-        """Attention of this rank's share (its q/k/v rows in bufs["qkv"]) through the two exchanges.  full: (rows, Wl) fused
-        buffer of this rank's heads; the live rows of every rank land at [q0, q0 + sum(shares)) in rank order."""
+    def _sp_attention(self, bufs, shares, full_of, q0: int, pm, segments, ctx_out, item_rows=None, keep=None):
+        """(qkv_dst, attention) of a sharded pass for _layers: the share's q/k/v rows go to bufs["qkv"], and attention runs
+        through the two exchanges.  full_of(li): the layer's (rows, Wl) fused buffer of this rank's heads; the live rows of
+        every rank land at [q0, q0 + sum(shares)) in rank order.  keep(li): called once attention has run on them."""
         from . import sequence_parallel as SPM
-        cfg, sp = self.cfg, self.sp
-        P, g, Wl = sp["P"], sp["group"], sp["Wl"]
-        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        P, g, Wl = self.sp["P"], self.sp["group"], self.sp["Wl"]
+        nq, nk, hd = self.heads
         sizes = [e_ - a_ for a_, e_ in shares]
-        Mtot = sum(sizes)
-        ops.sp_pack_qkv(bufs["qkv"], P, nq, nk, hd, out=bufs["send"])
-        SPM.exchange_split(bufs["send"], full[q0:q0 + Mtot], [[n * Wl] * P for n in sizes], g)
-        Rf = full.shape[0]
+        Mtot, dc = sum(sizes), nq // P * hd
         kw = {} if item_rows is None else {"item_rows": item_rows}
-        ops.attention_qkv_range(full.view(1, Rf, Wl), pm, nq // P, nk // P, hd, q0, bufs["ctx_all"], segments=segments,
-                                **kw)
-        dc = nq // P * hd
-        SPM.exchange_split(bufs["ctx_all"], bufs["ctx_recv"], [[n * dc for n in sizes] for _ in range(P)], g)
-        ops.sp_unpack_ctx(bufs["ctx_recv"], P, out=ctx_out.view(-1, nq * hd))
 
-    def _sp_layers(self, hid, nrm, ctx, act, bufs, shares, rope, full_of, q0, pm, segments, after_qkv=None):
-        """The decoder layers of a per-clip pass on this rank's share `hid` (separate RMSNorm kernels, as the replicated
-        passes).  full_of(li): the layer's fused buffer; after_qkv(li, full): called once the layer's rows are in."""
-        m, cfg = self.model, self.cfg
-        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        for li, layer in enumerate(m.llm.layers):
-            at, mlp = layer.self_attn, layer.mlp
-            ops.rmsnorm(hid, layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=nrm)
-            ops.linear_qkv_rope(nrm, at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=bufs["qkv"])
+        def attention(li):
             full = full_of(li)
-            self._sp_attention(bufs, shares, full, q0, pm, segments, ctx)
-            if after_qkv is not None:
-                after_qkv(li, full)
-            ops.linear(ctx, at.o_proj.weight, residual=hid, out=hid)
-            ops.rmsnorm(hid, layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon, out=nrm)
-            ops.gated_mlp_act(nrm, mlp.gate_up_proj.weight, mlp.act, out=act)
-            ops.linear(act, mlp.down_proj.weight, residual=hid, out=hid)
-
-    def _sp_pass_buffers(self, Mtot: int):
-        """Share and workspaces of this rank in a per-clip pass over Mtot rows."""
-        cfg, H = self.cfg, self.H
-        shares, _ = sp_shares(Mtot, self.sp["P"])
-        a, b = shares[self.sp["r"]]
-        e = lambda *s_: torch.empty(*s_, dtype=BF16, device=self.dev)
-        mm = b - a
-        return shares, a, b, (e(1, mm, H), e(1, mm, cfg.num_attention_heads * cfg.head_dim),
-                              e(1, mm, cfg.intermediate_size)), self._sp_buffers(Mtot, mm)
-
-    def _sp_prefill(self):
-        """prefill() sharded: rows [0, S) cut into shares."""
-        m, H = self.model, self.H
-        S = self.S0 + (self.hoist["nf"] if self.hoist else 0)
-        hid_all = torch.empty(1, S, H, dtype=BF16, device=self.dev)
-        ops.embed_gather(self.input_ids[:, :S].contiguous(), m.llm.embed_tokens.weight, out=hid_all)
-        if self.cond is not None:
-            ops.patch_embed(self.cond, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, m.pos_embed[0],
-                            self.cond_rows, hid_all.view(-1, H), m.pos_embed_max_size)
-        shares, a, b, (nrm, ctx, act), bufs = self._sp_pass_buffers(S)
-        rope = (self.rope[0][a:b].contiguous(), self.rope[1][a:b].contiguous())
-        self._sp_layers(hid_all[:, a:b], nrm, ctx, act, bufs, shares, rope, lambda li: self.qkv_full[li], 0, self.pm,
-                        ((0, 0, S),))
-        torch.cuda.current_stream().synchronize()
-
-    def _sp_clip_pass(self):
-        """_clip_pass() sharded: the pass's Sc + T nf rows cut into shares; every rank keeps the cached rows and the time
-        rows of every step for its own heads."""
-        import numpy as np
-        m, cfg, H, dev = self.model, self.cfg, self.H, self.dev
-        Wl = self.sp["Wl"]
-        S0, nf, T = self.S0, self.hoist["nf"], self.num_steps
-        Sc = S0 + nf
-        Lp = Sc + T * nf
-        idx = np.concatenate([np.arange(Sc), np.tile(np.arange(Sc, Sc + nf), T)])
-        lp = self.layout.permute(idx)
-        sub = lp.sub.copy()
-        sub[0, Sc:] = 1 + np.repeat(np.arange(T), nf)
-        pm = lp.with_subgroups(sub).packed_mask(dev)
-        e = lambda *s_: torch.empty(*s_, dtype=BF16, device=dev)
-        hid_all = e(1, Lp, H)
-        ops.embed_gather(self.input_ids[:, :Sc].contiguous(), m.llm.embed_tokens.weight, out=hid_all[:, :Sc])
-        if self.cond is not None:
-            ops.patch_embed(self.cond, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, m.pos_embed[0],
-                            self.cond_rows, hid_all.view(-1, H), m.pos_embed_max_size)
-        ts = self.sigma[:T].contiguous()
-        sin, tt_h, tt_o = e(T, 256), e(T, H), e(T, H)
-        ops.timestep_sinusoid(ts, m.time_token.freqs(dev), out=sin)
-        tt = m.time_token.mlp
-        for c in range(0, T, 32):
-            ops.linear_small(sin[c:c + 32], tt[0].weight, tt[0].bias, post_act=ops.ACT_SILU, out=tt_h[c:c + 32])
-            ops.linear_small(tt_h[c:c + 32], tt[2].weight, tt[2].bias, out=tt_o[c:c + 32])
-        hid_all[0, Sc:].view(T, nf, H)[:] = tt_o[:, None, :]
-        shares, a, b, (nrm, ctx, act), bufs = self._sp_pass_buffers(Lp)
-        rope = tuple(torch.cat([t_[:Sc], t_[Sc:Sc + nf].repeat(T, 1)])[a:b].contiguous() for t_ in self.rope)
-        buf = e(Lp, Wl)
-        shape = (T, cfg.num_hidden_layers, nf, Wl)
-        if self.time_qkv is None or tuple(self.time_qkv.shape) != shape:
-            self.time_qkv = e(*shape)
-
-        def keep(li, full):
-            self.qkv_full[li][:Sc].copy_(full[:Sc])
-            self.time_qkv[:, li].copy_(full[Sc:].view(T, nf, Wl))
-        self._sp_layers(hid_all[:, a:b], nrm, ctx, act, bufs, shares, rope, lambda li: buf, 0, pm, ((0, 0, Lp),),
-                        after_qkv=keep)
-        self.time_dst = self.qkv_full[:, Sc:Sc + nf]
-        torch.cuda.current_stream().synchronize()
-
-    def _sp_forward_step(self, from_tables: bool):
-        """forward_step() sharded (see the block comment above)."""
-        from . import sequence_parallel as SPM
-        m, cfg, H, sp = self.model, self.cfg, self.H, self.sp
-        seq2d = self.hid_all.view(-1, H)
-        pos = m.pos_embed[0]
-        S = self.S
-        x_rows, t_rows = (self.x_rows_a, self.t_rows_a) if S else (self.x_rows, self.t_rows)
-        if not self.hoist:
-            ops.embed_gather(self.ids_a if S else self.input_ids, m.llm.embed_tokens.weight, out=self.hid_all)
-        if self.cond is not None and not S:
-            ops.patch_embed(self.cond, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, pos,
-                            self.cond_rows, seq2d, m.pos_embed_max_size)
-        from_tables = from_tables and self.mod_all is not None
-        if not (from_tables and self.hoist):
-            ops.timestep_sinusoid(self.ts, m.time_token.freqs(self.dev), out=self.temb_sin)
-        if self.hoist:
-            if self.time_qkv is None:
-                raise VgptError("StaticDenoiser: set_sigma() must run before the first step")
-            ops.sampler_copy_step_rows(self.time_qkv, self.time_dst, self.step)
-        else:
-            tt = m.time_token.mlp
-            ops.linear_small(self.temb_sin, tt[0].weight, tt[0].bias, post_act=ops.ACT_SILU, out=self.tt_h)
-            ops.linear_small(self.tt_h, tt[2].weight, tt[2].bias, out=seq2d, out_row=t_rows, ldo=H)
-        ops.patch_embed(self.z_model, m.x_embedder.proj.weight, m.x_embedder.proj.bias, pos, x_rows, seq2d,
-                        m.pos_embed_max_size)
-        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        fz, hid, rope, bufs = self.fuse, self.hid, self.sp_rope, self.sp_bufs
-        if fz is not None:
-            ops.rms_rstd(hid, m.llm.layers[0].input_layernorm.variance_epsilon, out=fz["rstd_in"])
-        segs = self.seg_live if S else self.seg_all
-        for li_, layer in enumerate(m.llm.layers):
-            at, mlp = layer.self_attn, layer.mlp
-            if fz is None:
-                ops.rmsnorm(hid, layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=self.nrm)
-                ops.linear_qkv_rope(self.nrm, at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=bufs["qkv"])
-            else:
-                ops.linear_qkv_rope_prenorm(hid, fz["wq"][li_], rope[0], rope[1], fz["rstd_in"], nq, nk, hd, out=bufs["qkv"])
-            self._sp_attention(bufs, sp["shares"], self.qkv_full[li_ if S else 0], S, self.pm, segs, self.ctx,
-                               item_rows=self.attn_item_rows)
-            if fz is not None:
-                ops.linear_resid_rstd(self.ctx, at.o_proj.weight, hid, fz["rstd_post"], fz["ws"],
-                                      layer.post_attention_layernorm.variance_epsilon, out=hid)
-                ops.gated_mlp_act_prenorm(hid, fz["wgu"][li_], fz["rstd_post"], mlp.act, out=self.act)
-                nxt = m.llm.layers[min(li_ + 1, len(m.llm.layers) - 1)].input_layernorm.variance_epsilon
-                ops.linear_resid_rstd(self.act, mlp.down_proj.weight, hid, fz["rstd_in"], fz["ws"], nxt, out=hid)
-                continue
-            ops.linear(self.ctx, at.o_proj.weight, residual=hid, out=hid)
-            ops.rmsnorm(hid, layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon,
-                        out=self.nrm)
-            ops.gated_mlp_act(self.nrm, mlp.gate_up_proj.weight, mlp.act, out=self.act)
-            ops.linear(self.act, mlp.down_proj.weight, residual=hid, out=hid)
-        a, b = sp["a"], sp["b"]
-        ops.rmsnorm(hid, m.llm.norm.weight, m.llm.norm.variance_epsilon, out=self.nrm_all[:, a:b])
-        if from_tables:
-            ops.sampler_copy_step_rows(self.mod_all, self.mod.view(1, self.nf, 2 * H), self.step)
-        else:
-            te = m.t_embedder.mlp
-            ops.linear_small(self.temb_sin[:1], te[0].weight, te[0].bias, post_act=ops.ACT_SILU, out=self.te_h[:1])
-            ops.linear_small(self.te_h[:1], te[2].weight, te[2].bias, out=self.temb[:1])
-            ada = m.final_layer.adaLN_modulation[1]
-            ops.linear_small(self.temb[:1], ada.weight, ada.bias, pre_act=ops.ACT_SILU, out=self.mod[:1])
-            if self.nf > 1:
-                self.mod[1:].copy_(self.mod[:1].expand(self.nf - 1, -1))
-        f0, f1 = self.sp_frames
-        if f1 > f0:
-            ops.final_layer(self.nrm_all.view(-1, H), x_rows[f0:f1], self.mod[f0:f1], m.final_layer.linear.weight,
-                            m.final_layer.linear.bias, self.pred_loc[f0:f1])
-        every = SPM.all_gather_flat(self.pred_loc, sp["group"])          # (P, elements of pred)
-        torch.gather(every, 0, self.sp_owner, out=self.pred.view(1, -1))
+            ops.sp_pack_qkv(bufs["qkv"], P, nq, nk, hd, out=bufs["send"])
+            SPM.exchange_split(bufs["send"], full[q0:q0 + Mtot], [[n * Wl] * P for n in sizes], g)
+            ops.attention_qkv_range(full.view(1, full.shape[0], Wl), pm, nq // P, nk // P, hd, q0, bufs["ctx_all"],
+                                    segments=segments, **kw)
+            SPM.exchange_split(bufs["ctx_all"], bufs["ctx_recv"], [[n * dc for n in sizes] for _ in range(P)], g)
+            ops.sp_unpack_ctx(bufs["ctx_recv"], P, out=ctx_out.view(-1, nq * hd))
+            if keep is not None:
+                keep(li)
+        return (lambda li: bufs["qkv"]), attention
 
     def set_latents(self, z: torch.Tensor):
         """z: (n_frames, C, h, w) any float dtype; becomes the fp32 sampler state."""
@@ -846,23 +764,17 @@ class StaticDenoiser:
         self.steps_taken = 0
 
     # ---- one denoise forward: z_model, ts -> pred ----
-    def forward_step(self, from_tables: bool = False):
-        """from_tables: the step is sigma[*step] of the table (sampler_step), so everything that depends on the step
-        alone comes from the per-clip passes; otherwise `self.ts` may hold any timesteps."""
-        if self.sp is not None:
-            return self._sp_forward_step(from_tables)
-        m, cfg, H = self.model, self.cfg, self.H
-        seq2d = self.hid.view(-1, H)
-        pos = m.pos_embed[0]
-        S = self.S
+    def _step_head(self, from_tables: bool):
+        """Sequence assembly of the live rows (all of them, on every rank): token embeddings, condition patches, time tokens
+        (or, hoisted, the time rows' q/k/v of this step dropped into qkv_full), noisy patches."""
+        m, H, S = self.model, self.H, self.S
+        hid = self.hid if self.sp is None else self.hid_all
+        seq2d = hid.view(-1, H)
         x_rows, t_rows = (self.x_rows_a, self.t_rows_a) if S else (self.x_rows, self.t_rows)
-        rope = self.rope_a if S else self.rope
         if not self.hoist:   # a hoisted step's live rows are image rows only: the patch embedding below writes every one
-            ops.embed_gather(self.ids_a if S else self.input_ids, m.llm.embed_tokens.weight, out=self.hid)
-        if self.cond is not None and not S:
-            ops.patch_embed(self.cond, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, pos,
-                            self.cond_rows, seq2d, m.pos_embed_max_size)
-        from_tables = from_tables and self.mod_all is not None
+            ops.embed_gather(self.ids_a if S else self.input_ids, m.llm.embed_tokens.weight, out=hid)
+        if not S:
+            self._embed_cond(seq2d)
         if not (from_tables and self.hoist):
             ops.timestep_sinusoid(self.ts, m.time_token.freqs(self.dev), out=self.temb_sin)
         if self.hoist:
@@ -873,74 +785,20 @@ class StaticDenoiser:
             tt = m.time_token.mlp
             ops.linear_small(self.temb_sin, tt[0].weight, tt[0].bias, post_act=ops.ACT_SILU, out=self.tt_h)
             ops.linear_small(self.tt_h, tt[2].weight, tt[2].bias, out=seq2d, out_row=t_rows, ldo=H)
-        ops.patch_embed(self.z_model, m.x_embedder.proj.weight, m.x_embedder.proj.bias, pos, x_rows, seq2d,
+        ops.patch_embed(self.z_model, m.x_embedder.proj.weight, m.x_embedder.proj.bias, m.pos_embed[0], x_rows, seq2d,
                         m.pos_embed_max_size)
-        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        fz = self.fuse
-        if fz is not None:
-            # the statistics of the first norm: the embedded rows are no GEMM's output.  From here on every residual stream is
-            # written by linear_resid_ssq, which leaves the next norm's partial sums of squares behind
-            ops.rms_rstd(self.hid, m.llm.layers[0].input_layernorm.variance_epsilon, out=fz["rstd_in"])
 
-        mx = self.mx8
-
-        def qkv_proj(li_, layer, out):
-            at = layer.self_attn
-            if mx is not None:
-                ops.mx8_quantize_rows(self.hid, mx["a_hid"], mx["rstd"], layer.input_layernorm.variance_epsilon)
-                return ops.linear_mx8(mx["a_hid"], mx["w"][li_]["qkv"], out, "rope", rstd=mx["rstd"], cos=rope[0], sin=rope[1],
-                                      n_rot_heads=nq + nk, head_dim=hd)
-            if fz is None:
-                return ops.linear_qkv_rope(self.nrm, at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=out)
-            return ops.linear_qkv_rope_prenorm(self.hid, fz["wq"][li_], rope[0], rope[1], fz["rstd_in"], nq, nk, hd, out=out)
-        for li_, layer in enumerate(m.llm.layers):
-            at, mlp = layer.self_attn, layer.mlp
-            if fz is None and mx is None:
-                ops.rmsnorm(self.hid, layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=self.nrm)
-            if S:
-                full = self.qkv_full[li_]
-                live = full[S:]                                  # this step's q/k/v rows, behind the cached prefix
-                qkv_proj(li_, layer, live)
-                if self.attn_fp8:
-                    # the prefix rows were quantised once by prefill(); a step re-quantises from the first row it writes
-                    ops.attention_qkv_fp8(full.view(1, self.L, -1), self.pm, nq, nk, hd, out=self.ctx, q_start=S,
-                                          segments=self.seg_live, workspace=self.fp8_ws[li_], quant_from=self.fp8_from)
-                else:
-                    ops.attention_qkv_range(full.view(1, self.L, -1), self.pm, nq, nk, hd, S, self.ctx, segments=self.seg_live,
-                                            item_rows=self.attn_item_rows)
-            else:
-                qkv_proj(li_, layer, self.qkv)
-                if self.attn_fp8:
-                    ops.attention_qkv_fp8(self.qkv, self.pm, nq, nk, hd, out=self.ctx, segments=self.seg_all)
-                elif self.seg_all is not None:
-                    ops.attention_qkv_range(self.qkv, self.pm, nq, nk, hd, 0, self.ctx, segments=self.seg_all,
-                                            item_rows=self.attn_item_rows)
-                else:
-                    ops.attention_qkv(self.qkv, self.pm, nq, nk, hd, out=self.ctx)
-            if mx is not None:
-                w = mx["w"][li_]
-                ops.mx8_quantize_rows(self.ctx, mx["a_ctx"])
-                ops.linear_mx8(mx["a_ctx"], w["o"], self.hid, "resid", residual=self.hid)
-                ops.mx8_quantize_rows(self.hid, mx["a_hid"], mx["rstd"], layer.post_attention_layernorm.variance_epsilon)
-                ops.linear_mx8(mx["a_hid"], w["gate_up"], self.act, "gated", rstd=mx["rstd"], act=mlp.act)
-                ops.mx8_quantize_rows(self.act, mx["a_act"])
-                ops.linear_mx8(mx["a_act"], w["down"], self.hid, "resid", residual=self.hid)
-                continue
-            if fz is not None:
-                ops.linear_resid_rstd(self.ctx, at.o_proj.weight, self.hid, fz["rstd_post"], fz["ws"],
-                                      layer.post_attention_layernorm.variance_epsilon, out=self.hid)
-                ops.gated_mlp_act_prenorm(self.hid, fz["wgu"][li_], fz["rstd_post"], mlp.act, out=self.act)
-                # the statistic the NEXT layer's input norm reads (its eps; the last layer's goes unused: the final norm is a
-                # separate kernel)
-                nxt = m.llm.layers[min(li_ + 1, len(m.llm.layers) - 1)].input_layernorm.variance_epsilon
-                ops.linear_resid_rstd(self.act, mlp.down_proj.weight, self.hid, fz["rstd_in"], fz["ws"], nxt, out=self.hid)
-                continue
-            ops.linear(self.ctx, at.o_proj.weight, residual=self.hid, out=self.hid)
-            ops.rmsnorm(self.hid, layer.post_attention_layernorm.weight,
-                        layer.post_attention_layernorm.variance_epsilon, out=self.nrm)
-            ops.gated_mlp_act(self.nrm, mlp.gate_up_proj.weight, mlp.act, out=self.act)
-            ops.linear(self.act, mlp.down_proj.weight, residual=self.hid, out=self.hid)
-        ops.rmsnorm(self.hid, m.llm.norm.weight, m.llm.norm.variance_epsilon, out=self.nrm)
+    def _step_tail(self, from_tables: bool):
+        """Final norm, the final layer's adaLN modulation (from the per-clip table, or the small MLPs on self.ts), final layer
+        + unpatchify into `pred`.  Sharded: each rank runs the final layer on the frames it owns rows of, and one all-gather
+        (owner-selected per element) leaves the full `pred` on every rank."""
+        m, H, sp = self.model, self.H, self.sp
+        x_rows = self.x_rows_a if self.S else self.x_rows
+        if sp is None:
+            (f0, f1), nrm_all, nrm, pred = (0, self.nf), self.nrm, self.nrm, self.pred
+        else:
+            (f0, f1), nrm_all, nrm, pred = self.sp_frames, self.nrm_all, self.nrm_all[:, sp["a"]:sp["b"]], self.pred_loc
+        ops.rmsnorm(self.hid, m.llm.norm.weight, m.llm.norm.variance_epsilon, out=nrm)
         # t_embedder + adaLN modulation: every frame of a step carries the same t (LVM/scheduler.py:169), so one row is
         # computed and broadcast (the small-M kernel re-reads its input rows for every output column)
         if from_tables:
@@ -953,8 +811,49 @@ class StaticDenoiser:
             ops.linear_small(self.temb[:1], ada.weight, ada.bias, pre_act=ops.ACT_SILU, out=self.mod[:1])
             if self.nf > 1:
                 self.mod[1:].copy_(self.mod[:1].expand(self.nf - 1, -1))
-        ops.final_layer(self.nrm.view(-1, H), x_rows, self.mod, m.final_layer.linear.weight,
-                        m.final_layer.linear.bias, self.pred)
+        if f1 > f0:
+            ops.final_layer(nrm_all.view(-1, H), x_rows[f0:f1], self.mod[f0:f1], m.final_layer.linear.weight,
+                            m.final_layer.linear.bias, pred[f0:f1])
+        if sp is not None:
+            from . import sequence_parallel as SPM
+            every = SPM.all_gather_flat(self.pred_loc, sp["group"])          # (P, elements of pred)
+            torch.gather(every, 0, self.sp_owner, out=self.pred.view(1, -1))
+
+    def forward_step(self, from_tables: bool = False):
+        """from_tables: the step is sigma[*step] of the table (sampler_step), so everything that depends on the step
+        alone comes from the per-clip passes; otherwise `self.ts` may hold any timesteps."""
+        from_tables = from_tables and self.mod_all is not None
+        self._step_head(from_tables)
+        nq, nk, hd = self.heads
+        S, pm, ctx, rows = self.S, self.pm, self.ctx, self.attn_item_rows
+        rope = self.rope_a if S else self.rope
+        if self.sp is not None:
+            rope = tuple(t_[self.sp["a"]:self.sp["b"]] for t_ in rope)
+            qkv_dst, attention = self._sp_attention(self.sp_bufs, self.sp["shares"], lambda li: self.qkv_full[li if S else 0], S,
+                                                    pm, self.seg_live if S else self.seg_all, ctx, item_rows=rows)
+        elif S:
+            qkv_dst = lambda li: self.qkv_full[li][S:]       # this step's q/k/v rows, behind the cached prefix
+
+            def attention(li):
+                full = self.qkv_full[li].view(1, self.L, -1)
+                if self.attn_fp8:
+                    # the prefix rows were quantised once by prefill(); a step re-quantises from the first row it writes
+                    ops.attention_qkv_fp8(full, pm, nq, nk, hd, out=ctx, q_start=S, segments=self.seg_live,
+                                          workspace=self.fp8_ws[li], quant_from=self.fp8_from)
+                else:
+                    ops.attention_qkv_range(full, pm, nq, nk, hd, S, ctx, segments=self.seg_live, item_rows=rows)
+        else:
+            qkv_dst = lambda li: self.qkv
+
+            def attention(li):
+                if self.attn_fp8:
+                    ops.attention_qkv_fp8(self.qkv, pm, nq, nk, hd, out=ctx, segments=self.seg_all)
+                elif self.seg_all is not None:
+                    ops.attention_qkv_range(self.qkv, pm, nq, nk, hd, 0, ctx, segments=self.seg_all, item_rows=rows)
+                else:
+                    ops.attention_qkv(self.qkv, pm, nq, nk, hd, out=ctx)
+        self._layers(self.hid, self.nrm, ctx, self.act, rope, qkv_dst, attention, fz=self.fuse, mx=self.mx8)
+        self._step_tail(from_tables)
 
     def sampler_step(self):
         """LVM/scheduler.py:168-204 for one i: timesteps, model call, x1->v, CFG, Euler, i += 1."""
@@ -964,17 +863,22 @@ class StaticDenoiser:
                              self.cfg_scale)
         ops.sampler_advance(self.step)
 
+    def _step_then_capture(self, restore: bool):
+        """One eager step (kernels set their launch attributes on first use, which a capture cannot record), then the capture
+        of a step, which records without executing.  restore: the eager step leaves no trace in the sampler state."""
+        saved = (self.z.clone(), self.z_model.clone(), self.step.clone()) if restore else None
+        self.sampler_step()
+        torch.cuda.current_stream().synchronize()
+        if restore:
+            self.z.copy_(saved[0]); self.z_model.copy_(saved[1]); self.step.copy_(saved[2])
+            torch.cuda.current_stream().synchronize()
+        self.graph = ops.HipGraph().capture(self.sampler_step)
+
     def capture(self):
         """Capture one sampler step into a hipGraph (must run on a non-default stream)."""
         if self.sp is not None:
             raise VgptError("StaticDenoiser.capture: a sequence-parallel engine runs eagerly (its exchanges are not captured)")
-        # one eager step first: kernels set their attributes on first launch, which is not capturable
-        saved = (self.z.clone(), self.z_model.clone(), self.step.clone())
-        self.sampler_step()
-        torch.cuda.current_stream().synchronize()
-        self.z.copy_(saved[0]); self.z_model.copy_(saved[1]); self.step.copy_(saved[2])
-        torch.cuda.current_stream().synchronize()
-        self.graph = ops.HipGraph().capture(self.sampler_step)
+        self._step_then_capture(restore=True)
         return self
 
     def run(self, num_steps: Optional[int] = None, use_graph: bool = True):
@@ -985,11 +889,7 @@ class StaticDenoiser:
         self.steps_taken += n
         use_graph = use_graph and self.sp is None   # sharded engines run eagerly: collectives are not captured (yet)
         if use_graph and self.graph is None and n > 0:
-            # the first step runs eagerly (kernels set their launch attributes on first use, which a capture cannot
-            # record) and counts as a real step; the capture that follows records without executing
-            self.sampler_step()
-            torch.cuda.current_stream().synchronize()
-            self.graph = ops.HipGraph().capture(self.sampler_step)
+            self._step_then_capture(restore=False)   # the eager step counts as a real one
             n -= 1
         for _ in range(n):
             if use_graph:

@@ -39,7 +39,8 @@ class LVMScheduler:
         self.linear_precision = "bf16"       # "fp8": MX-fp8 qkv / o / gate_up / down projections in the fast path's steps
         self.fuse_norms = None               # None: RMSNorms folded into the GEMMs wherever the step's shapes allow (engine.py); False: never
         # True: under a sequence-parallel group of P > 1 ranks (sequence_parallel.py) the fast path builds the sharded engine
-        # (Ulysses: every rank runs ~1/P of the live rows and 1/P of the attention heads, engine.StaticDenoiser._sp_plan).
+        # (Ulysses: every rank runs ~1/P of the live rows and 1/P of the attention heads: the same StaticDenoiser passes on the
+        # rank's share of the rows, attention through StaticDenoiser._sp_attention).
         # Sharded engines run eagerly, whatever use_graph says: capturing the RCCL exchanges into a hipGraph is a separate
         # step.  False (default): every rank runs the whole clip, as before.
         self.sequence_parallel_engine = False
