@@ -521,6 +521,32 @@ int vgpt_adamw_step(float* master, void* param, const void* grad, int grad_f32, 
                     float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale,
                     void* stream);
 
+/* ---- LoRA adapters (LVM/train/train_x1_stage1_noiseinput.py:204-223, peft LoraConfig on qkv_proj / o_proj; the merge of
+ *      LVM/pipeline.py:97-101) ------------------------------------------------------------------------------------------
+ * Three products with one skinny side.  Every small operand carries a PADDED rank rp in {16, 32, 48, 64} (anything else:
+ * VGPT_ERR_UNSUPPORTED); the caller owns the padding: ranks r..rp-1 of every small operand are zero and stay zero, the
+ * kernels read rp-wide vectors unmasked.  bf16 operands, fp32 accumulation; the big operand has a row stride in elements
+ * (ld >= width, ld % 8 == 0; widths are multiples of 8; every pointer 16-byte aligned).
+ *   vgpt_lora_down: U (M, rp) bf16 = alpha X (M, K; ldx) S, with S stored (rp, K) row-major (s_is_k_by_rp = 0: u = x A^T, A as
+ *       peft stores it) or (K, rp) row-major (s_is_k_by_rp = 1: du = dy B).  X is read once.
+ *   vgpt_lora_up_add: in place, Y (M, N; ldy) = bf16(rope?(float(Y) + alpha U (M, rp) S)), S stored (N, rp) (s_is_rp_by_n = 0)
+ *       or (rp, N) (s_is_rp_by_n = 1); one read and one write of Y.  cos_t / sin_t NULL: no rotation.  Otherwise (M, head_dim / 2)
+ *       fp32 tables of vgpt_rope_table and N = (n_heads + 2 n_kv_heads) head_dim: the q and k heads are rotated as in
+ *       vgpt_gemm_bf16_rope (pairs d, d + head_dim / 2; on the fp32 sum, one rounding), the v columns are not.  head_dim % 16 == 0,
+ *       head_dim <= 128.  Serves y += s u B^T (forward), dx += du A (backward) and the merge W += s B A (Y = W, U = B, S = A).
+ *   vgpt_lora_grad: G (N, rp) fp32 = alpha Y (M, N; ldy)^T U (M, rp; ldu), stored (rp, N) when store_transposed != 0
+ *       (dB = s dy^T u, dA = du^T x).  The reduction over M is cut into slices, a function of (M, N) alone, that are added in a
+ *       fixed order: the result is bit-identical from run to run.  workspace: vgpt_lora_grad_workspace_bytes(M, N, rp) bytes
+ *       (0: none needed), 16-byte aligned; a smaller one is VGPT_ERR_INVALID. */
+int vgpt_lora_down(const void* X, const void* S, void* U, int64_t M, int64_t K, int rp, int64_t ldx, int s_is_k_by_rp,
+                   float alpha, void* stream);
+int vgpt_lora_up_add(void* Y, const void* U, const void* S, const float* cos_t, const float* sin_t, int64_t M, int64_t N,
+                     int rp, int64_t ldy, int s_is_rp_by_n, int n_heads, int n_kv_heads, int head_dim, float alpha,
+                     void* stream);
+int64_t vgpt_lora_grad_workspace_bytes(int64_t M, int64_t N, int rp);
+int vgpt_lora_grad(const void* Y, const void* U, float* G, int64_t M, int64_t N, int rp, int64_t ldy, int64_t ldu,
+                   int store_transposed, float alpha, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- hipGraph helpers (sampler loop under graph capture) ----------------- */
 int vgpt_graph_begin_capture(void* stream);
 int vgpt_graph_end_capture(void* stream, void** graph_exec_out);

@@ -59,6 +59,11 @@ class LVMPipeline:
             raise FileNotFoundError("no VAE directory given and stabilityai/sdxl-vae cannot be downloaded offline")
         return cls(vae, model, processor)
 
+    def merge_lora(self, lora_path: str):
+        """Fold a trained adapter directory into the model's weights before sampling (LVM/pipeline.py:97-101)."""
+        from .lora import load_adapter, merge_adapter
+        merge_adapter(self.model, load_adapter(lora_path))
+
     def to(self, device: Union[str, torch.device]):
         self.device = torch.device(device)
         self.model.to(self.device)

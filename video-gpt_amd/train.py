@@ -16,7 +16,10 @@ optimizer to DeepSpeed's bf16 AdamW (fp32 master weights).  Here:
     on the reference's stage-2 exchange) reduce-scatters those buckets instead, keeps the fp32 master
     weights and moments of this rank's shard only and all-gathers the updated bf16 parameters;
   * clipping uses the norm of the averaged gradient; the 1/world factor and the clip coefficient are
-    folded into the AdamW kernel's gradient scale (no separate pass over the gradients).
+    folded into the AdamW kernel's gradient scale (no separate pass over the gradients);
+  * lora_rank=r (train_x1_stage1_noiseinput.py:204-223) freezes the base model and trains rank-r adapters on qkv_proj /
+    o_proj through the three products of ops_lora.py: no dW GEMM, no base optimizer state, one small bucket to exchange
+    (DESIGN.md §6a).
 """
 from __future__ import annotations
 
@@ -29,6 +32,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from . import ops_lora as LO
 from . import ops_train as T
 from . import sequence_parallel as SPM
 from .engine import _rows, bump_weight_generation, count_left_pads, pack_left_padded
@@ -36,6 +40,12 @@ from .ops import BF16, VgptError
 
 F32 = torch.float32
 DP_SHARDING_MODES = ("none", "optimizer")
+LORA_TARGETS = ("qkv_proj", "o_proj")
+
+
+def lora_key(layer: int, module: str, ab: str) -> str:
+    """peft's state-dict key of an adapter matrix of this model (get_peft_model_state_dict: adapter name stripped)."""
+    return f"base_model.model.llm.layers.{layer}.self_attn.{module}.lora_{ab}.weight"
 # dp_sharding="optimizer": every flat bucket is padded to a multiple of world * SHARD_GRANULE elements, so each rank's
 # shard starts 512 (bf16) / 1024 (fp32) bytes apart: vgpt_adamw_step's alignment check and vgpt_sumsq's 16-byte loads
 SHARD_GRANULE = 256
@@ -77,7 +87,8 @@ class Stage1Trainer:
                  max_grad_norm: Optional[float] = 1.0, input_noise: float = 0.9, pack_padding: bool = True,
                  lr_scheduler: str = "constant", lr_warmup_steps: int = 0, gradient_checkpointing: Optional[bool] = None,
                  forward_only: bool = False, lr_scheduler_steps_per_optimizer_step: int = 1,
-                 overlap_optimizer: bool = False, dp_sharding: Optional[str] = None):
+                 overlap_optimizer: bool = False, dp_sharding: Optional[str] = None, lora_rank: Optional[int] = None,
+                 lora_alpha: Optional[float] = None, lora_target_modules=LORA_TARGETS):
         """lr_scheduler / lr_warmup_steps: diffusers' get_scheduler("constant" | "constant_with_warmup")
         (train_x1_stage1_noiseinput.py:279-283; the scripts use constant_with_warmup): the k-th optimizer step (k = 0, 1,
         ...) runs at lr * min(1, k * lr_scheduler_steps_per_optimizer_step / warmup).
@@ -94,7 +105,10 @@ class Stage1Trainer:
         state (loss evaluation through `loss.training_losses_x1_noise_input`).  dp_sharding (default: $VGPT_DP_SHARDING,
         else "none"): "none" replicates the fp32 optimizer state on every rank and all-reduces the gradients; "optimizer"
         shards it (reduce-scatter of the gradient buckets, AdamW on this rank's 1/world of every bucket, all-gather of the
-        updated parameters).  Inert at world size 1."""
+        updated parameters).  Inert at world size 1.  lora_rank = r (1 <= r <= 64; train...py:204-223): the
+        base model is frozen and rank-r adapters on lora_target_modules of every decoder layer are the only trained tensors
+        (lora_alpha defaults to r; peft's "gaussian" init); no base gradient buckets, masters or moments exist, the adapter
+        state is a few MB and is never sharded."""
         model._check_ready()
         if hasattr(model, "release_engines"):
             model.release_engines()          # a sampler engine cached on the model holds GBs the trainer's buffers want
@@ -116,6 +130,15 @@ class Stage1Trainer:
         self.dev = model.llm.norm.weight.device
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.rank = dist.get_rank() if self.world > 1 else 0
+        if lora_rank is not None:
+            if isinstance(lora_rank, bool) or int(lora_rank) != lora_rank or not 1 <= int(lora_rank) <= 64:
+                raise VgptError(f"lora_rank {lora_rank!r}: an integer rank 1 <= r <= 64 is built")
+            bad = [n for n in lora_target_modules if n not in LORA_TARGETS]
+            if bad or not lora_target_modules:
+                raise VgptError(f"lora_target_modules {tuple(lora_target_modules)!r}: adapters are built for {LORA_TARGETS} only")
+            if dp_sharding == "optimizer":
+                raise VgptError('dp_sharding="optimizer" with lora_rank: the adapter state is a few MB, there is nothing to shard')
+            dp_sharding = "none"             # $VGPT_DP_SHARDING is ignored in this mode
         if dp_sharding is None:
             dp_sharding = os.environ.get("VGPT_DP_SHARDING", "none")
         if dp_sharding not in DP_SHARDING_MODES:
@@ -144,6 +167,11 @@ class Stage1Trainer:
         self._ws = {}
         self.last = {}
         self.grads: Dict[str, torch.Tensor] = {}
+        self.lora_rank = None
+        self.lora: Dict[str, torch.Tensor] = {}
+        if lora_rank is not None:
+            self._init_lora(int(lora_rank), lora_alpha, tuple(lora_target_modules))
+            return
         if forward_only:
             return
         L = self.cfg.num_hidden_layers
@@ -205,6 +233,101 @@ class Stage1Trainer:
         self.param_small = flat
         bump_weight_generation(model)     # storage re-pointed; from here on the optimizer writes it through raw pointers
         self._init_scalars()
+
+    # ---- LoRA mode --------------------------------------------------------------------------------------------------
+    def _init_lora(self, r: int, alpha, targets):
+        """One flat rp-padded bf16 working buffer for every adapter (layer order; per module lora_A (rp, in) then lora_B
+        (out, rp)), with one flat fp32 master, m, v and gradient bucket: AdamW, the clip's sum of squares and the
+        data-parallel exchange are one launch each.  The base parameters stay where they are and get no state at all."""
+        self.lora_rank, self.lora_rp = r, LO.padded_rank(r)
+        self.lora_alpha = float(r if alpha is None else alpha)
+        self.lora_scale = self.lora_alpha / r
+        self.lora_targets = tuple(n for n in LORA_TARGETS if n in targets)
+        rp = self.lora_rp
+        slots, o = [], 0            # (layer, module, "A" | "B", offset, padded shape)
+        for i, layer in enumerate(self.model.llm.layers):
+            for mod in self.lora_targets:
+                out_f, in_f = getattr(layer.self_attn, mod).weight.shape
+                for ab, shape in (("A", (rp, in_f)), ("B", (out_f, rp))):
+                    slots.append((i, mod, ab, o, shape))
+                    o += shape[0] * shape[1]
+        self._lora_numel = o
+        # peft init_lora_weights="gaussian": lora_A ~ N(0, (1/r)^2), lora_B = 0; CPU draws from torch's global generator in
+        # layer order; the padded ranks are zero and every kernel and the optimizer keep them exactly zero
+        host = torch.zeros(o, dtype=F32)
+        for i, mod, ab, off, shape in slots:
+            if ab == "A":
+                host[off:off + shape[0] * shape[1]].view(shape)[:r].normal_(0.0, 1.0 / r)
+        self.lora_param = host.to(BF16).to(self.dev)
+        train = not self.forward_only
+        if train:
+            self.lora_master = host.to(self.dev)
+            self.lora_m, self.lora_v = torch.zeros_like(self.lora_master), torch.zeros_like(self.lora_master)
+            self.lora_bucket = torch.zeros(o, dtype=F32, device=self.dev)
+        self._lora_w, self._lora_g = {}, {}      # (layer, module) -> padded (A, B) views of the working copy / the gradient
+        for i, mod, ab, off, shape in slots:
+            name = lora_key(i, mod, ab)
+            n = shape[0] * shape[1]
+            unpad = (lambda t: t[:r]) if ab == "A" else (lambda t: t[:, :r])
+            w = self.lora_param[off:off + n].view(shape)
+            self._lora_w.setdefault((i, mod), {})[ab] = w
+            self.lora[name] = unpad(w)
+            if train:
+                gr = self.lora_bucket[off:off + n].view(shape)
+                self._lora_g.setdefault((i, mod), {})[ab] = gr
+                self.grads[name] = unpad(gr)
+        if train:
+            self._init_scalars()
+
+    def _lora_optimizer_step(self, lr, b1, b2):
+        """sumsq, clip coefficient and AdamW over the one adapter bucket (the caller has advanced the step counter)."""
+        self.sumsq.zero_()
+        T.sumsq(self.lora_bucket, self.sumsq)
+        w = float(self.world)
+        T.clip_coef(self.sumsq, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w)
+        if not self.overlap_optimizer:
+            T.adamw_step(self.lora_master, self.lora_param, self.lora_bucket, self.lora_m, self.lora_v, lr, b1, b2, self.eps,
+                         self.wd, self.step_count, self.coef)
+            return
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream())
+        self._opt_stream.wait_event(ready)
+        with torch.cuda.stream(self._opt_stream):
+            T.adamw_step(self.lora_master, self.lora_param, self.lora_bucket, self.lora_m, self.lora_v, lr, b1, b2, self.eps,
+                         self.wd, self.step_count, self.coef)
+            ev = torch.cuda.Event()
+            ev.record(self._opt_stream)
+        self._opt_events = (ev, [ev] * self.cfg.num_hidden_layers)
+
+    def _merge_into(self, model, sign_scale=None):
+        """W <- bf16(float(W) + s B A) on every adapted projection of `model`, through lora_up_add (Y = W, U = B, S = A)."""
+        s = self.lora_scale if sign_scale is None else sign_scale
+        for (i, mod), w in self._lora_w.items():
+            LO.lora_up_add(getattr(model.llm.layers[i].self_attn, mod).weight.data, w["B"], w["A"], s_is_rp_by_n=True, alpha=s)
+
+    def merged_weights(self):
+        """Context manager for validation sampling mid-training: inside it the model's qkv_proj / o_proj weights carry the
+        current adapters (W + s B A); on exit the saved base weights come back bit for bit.  Cached sampler engines refold on
+        both edges (weight generation bumped)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            if self.lora_rank is None:
+                raise VgptError("merged_weights: not a LoRA trainer")
+            self.finish_optimizer()
+            ws = [getattr(self.model.llm.layers[i].self_attn, mod).weight for (i, mod) in self._lora_w]
+            saved = [w.detach().clone() for w in ws]
+            self._merge_into(self.model)
+            bump_weight_generation(self.model)
+            try:
+                yield self.model
+            finally:
+                with torch.no_grad():
+                    for w, sv_ in zip(ws, saved):
+                        w.copy_(sv_)
+                bump_weight_generation(self.model)
+        return cm()
 
     def _init_scalars(self):
         self.sumsq = torch.zeros(1, dtype=F32, device=self.dev)
@@ -363,15 +486,30 @@ class Stage1Trainer:
         gu = self._buf("gu", (ns, M, 2 * I)); act = self._buf("act", (ns, M, I))
         lse = self._buf("lse", (ns, B, nq, L), F32)
         sv = lambda li: 0 if ck else li
+        lora = self.lora_rank is not None
+        lq, lo = lora and "qkv_proj" in self.lora_targets, lora and "o_proj" in self.lora_targets
+        if lora:        # u = x A^T of both adapted projections, saved for the backward like the other activations
+            rp, ls = self.lora_rp, self.lora_scale
+            u_q = self._buf("u_q", (ns, M, rp)); u_o = self._buf("u_o", (ns, M, rp))
 
         def layer_forward(li, with_output=True):
             layer = m.llm.layers[li]
             at, mlp, k = layer.self_attn, layer.mlp, sv(li)
             self._await_params(li)           # this layer's parameters are updated (and gathered)
             ops.rmsnorm(hbuf[li], layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=n1[k])
-            ops.linear_qkv_rope(n1[k], at.qkv_proj.weight, prep["rope"][0], prep["rope"][1], nq, nk, hd, out=qkv[k])
+            if lq:      # plain base GEMM, then y += s (x A^T) B^T and the rotation in one pass over y
+                aq = self._lora_w[(li, "qkv_proj")]
+                ops.linear(n1[k], at.qkv_proj.weight, out=qkv[k])
+                LO.lora_down(n1[k], aq["A"], rp, out=u_q[k])
+                LO.lora_up_add(qkv[k], u_q[k], aq["B"], alpha=ls, rope=(prep["rope"][0], prep["rope"][1], nq, nk, hd))
+            else:
+                ops.linear_qkv_rope(n1[k], at.qkv_proj.weight, prep["rope"][0], prep["rope"][1], nq, nk, hd, out=qkv[k])
             T.attention_qkv_train(qkv[k].view(B, L, -1), prep["pm"], nq, nk, hd, ctx[k].view(B, L, -1), lse[k])
             ops.linear(ctx[k], at.o_proj.weight, residual=hbuf[li], out=h2[k])
+            if lo:
+                ao = self._lora_w[(li, "o_proj")]
+                LO.lora_down(ctx[k], ao["A"], rp, out=u_o[k])
+                LO.lora_up_add(h2[k], u_o[k], ao["B"], alpha=ls)
             ops.rmsnorm(h2[k], layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon,
                         out=n2[k])
             # gate_up_proj + act(gate) * up in one kernel that also keeps the bf16 [gate | up] for the backward: bit for bit
@@ -419,6 +557,11 @@ class Stage1Trainer:
         if self.forward_only or not backward:
             if update:
                 raise VgptError("Stage1Trainer.step: an optimizer step needs the backward pass")
+            return loss
+        if lora:
+            self._lora_backward(locals())
+            if update:
+                self.optimizer_step()
             return loss
         # ---------------- backward ----------------
         g = self.grads
@@ -495,6 +638,69 @@ class Stage1Trainer:
             self.optimizer_step()
         return loss
 
+    def _lora_backward(self, f):
+        """Backward with the base frozen: the dX chain of the full backward without a single dW GEMM, and per adapted
+        projection dB = s dy^T u, du = s dy B, dA = du^T x, dx += du A.  Nothing that only feeds frozen parameters is
+        computed: no head / adaLN / embedder / embedding gradients, no dx below layer 0's qkv_proj.  `f`: step()'s locals."""
+        m, cfg, prep = self.model, self.cfg, f["prep"]
+        B, L, M, H, I = f["B"], f["L"], f["M"], f["H"], f["I"]
+        nq, nk, hd, nl, ntok, nf = f["nq"], f["nk"], f["hd"], f["nl"], f["ntok"], f["nf"]
+        hbuf, n1, qkv, ctx, h2, n2, gu, act, lse = (f[k] for k in ("hbuf", "n1", "qkv", "ctx", "h2", "n2", "gu", "act", "lse"))
+        u_q, u_o, sv, ck, rp, ls = f["u_q"], f["u_o"], f["sv"], f["ck"], self.lora_rp, self.lora_scale
+        lq, lo = f["lq"], f["lo"]
+        dy16 = T.unpatchify_bwd(f["dpred"])                                  # (Tn, 16)
+        dv = T.matmul(dy16, f["fl"].weight)                                  # (Tn, H)
+        dnrm = self._buf("dnrm", (M, H)); dnrm.zero_()
+        dmod = self._buf("dmod_scratch", (nf, 2 * H), F32); dmod.zero_()     # feeds adaLN only: discarded
+        T.ln_mod_bwd(dv, f["xhat"], f["rstd"], f["mod"], prep["x_rows"], dnrm, dmod, ntok)
+        if f["head"] is not None:
+            dyin = T.unpatchify_bwd(f["dpred_in"])
+            dnrm.index_copy_(0, prep["c_idx"], T.matmul(dyin, f["head"].weight))
+        dgain = self._buf("dgain_scratch", (H,), F32); dgain.zero_()         # gain gradients of the frozen norms: discarded
+        dh = self._buf("dh", (M, H)); dh_b = self._buf("dh_b", (M, H))
+        T.rmsnorm_bwd(hbuf[nl], m.llm.norm.weight, dnrm, dh, dgain, m.llm.norm.variance_epsilon)
+        dact = self._buf("dact", (M, I)); dgu = self._buf("dgu", (M, 2 * I)); dn = self._buf("dn", (M, H))
+        dctx = self._buf("dctx", (M, nq * hd)); dqkv = self._buf("dqkv", (M, (nq + 2 * nk) * hd))
+        delta = self._buf("delta", (B, nq, L), F32)
+        du = self._buf("du", (M, rp))
+        nsin = self._neg_sin(prep)
+        self.lora_bucket.zero_()     # a target module left out keeps zero gradients; every built one is overwritten
+        for li in range(nl - 1, -1, -1):
+            layer = m.llm.layers[li]
+            at, mlp = layer.self_attn, layer.mlp
+            if ck:
+                f["layer_forward"](li, with_output=False)
+            k = sv(li)
+            T.linear_dx(dh, mlp.down_proj.weight, None, out=dact)
+            T.silu_mul_bwd(gu[k], dact, dgu, mlp.act)
+            T.linear_dx(dgu, mlp.gate_up_proj.weight, None, out=dn)
+            T.rmsnorm_bwd(h2[k], layer.post_attention_layernorm.weight, dn, dh_b, dgain,
+                          layer.post_attention_layernorm.variance_epsilon, dres=dh)       # dh2
+            T.linear_dx(dh_b, at.o_proj.weight, None, out=dctx)
+            if lo:
+                w, gr = self._lora_w[(li, "o_proj")], self._lora_g[(li, "o_proj")]
+                LO.lora_grad(dh_b, u_o[k], gr["B"], alpha=ls)                            # dB = s dy^T u
+                LO.lora_down(dh_b, w["B"], rp, s_is_k_by_rp=True, alpha=ls, out=du)      # du = s dy B
+                LO.lora_grad(ctx[k], du, gr["A"], transposed=True)                       # dA = du^T x
+                LO.lora_up_add(dctx, du, w["A"], s_is_rp_by_n=True)                      # dx += du A
+            T.attention_qkv_bwd(qkv[k].view(B, L, -1), ctx[k].view(B, L, -1), dctx.view(B, L, -1), lse[k], delta,
+                                dqkv.view(B, L, -1), prep["pm"], nq, nk, hd)
+            ops.rope_qk_inplace(dqkv, prep["rope"][0], nsin, nq, nk, hd)                 # inverse rotation
+            if lq:
+                w, gr = self._lora_w[(li, "qkv_proj")], self._lora_g[(li, "qkv_proj")]
+                LO.lora_grad(dqkv, u_q[k], gr["B"], alpha=ls)
+                LO.lora_down(dqkv, w["B"], rp, s_is_k_by_rp=True, alpha=ls, out=du)
+                LO.lora_grad(n1[k], du, gr["A"], transposed=True)
+            if li == 0:
+                break                # everything below layer 0's qkv_proj is frozen
+            T.linear_dx(dqkv, at.qkv_proj.weight, None, out=dn)
+            if lq:
+                LO.lora_up_add(dn, du, w["A"], s_is_rp_by_n=True)
+            T.rmsnorm_bwd(hbuf[li], layer.input_layernorm.weight, dn, dh, dgain, layer.input_layernorm.variance_epsilon,
+                          dres=dh_b)                                                     # dh (layer input)
+        if self.world > 1 and not self.skip_allreduce:
+            dist.all_reduce(self.lora_bucket)        # one small exchange per step
+
     def _neg_sin(self, prep):
         key = ("nsin", prep["rope"][1].data_ptr())
         if self._ws.get("nsin_key") != key:
@@ -529,6 +735,9 @@ class Stage1Trainer:
         lr = self.current_lr()
         self.last_lr = lr
         self.step_count += 1
+        if self.lora_rank is not None:
+            self._lora_optimizer_step(lr, *self.betas)
+            return
         self.sumsq.zero_()
         for b in self.layer_buckets:
             T.sumsq(self._shard(b), self.sumsq)
@@ -639,6 +848,12 @@ class Stage1Trainer:
         path = os.path.join(results_dir, f"checkpoint-{step}")
         distributed = dist.is_available() and dist.is_initialized()
         writer = not distributed or dist.get_rank() == 0
+        if self.lora_rank is not None:
+            if writer:
+                self._save_lora(path, step)
+            if distributed:
+                dist.barrier()
+            return path
         opt = {}
         for t, key, n in self._optimizer_tensors():
             if self._sharded:     # every rank takes part; one gathered bucket on the device at a time, then host memory
@@ -674,6 +889,11 @@ class Stage1Trainer:
         from safetensors.torch import load_file
         with open(os.path.join(path, "trainer_state.json")) as f:
             st = json.load(f)
+        if (self.lora_rank is not None) != ("lora" in st):
+            raise VgptError(f"{path}: a LoRA checkpoint resumes a LoRA trainer and a full one a full trainer")
+        if self.lora_rank is not None:
+            self._load_lora(path, st)
+            return self._restore_record(st, restore_hyperparameters)
         if st["small_names"] != self.small_names:
             raise VgptError("checkpoint was written for a different parameter layout")
         opt = load_file(os.path.join(path, "optimizer.safetensors"))
@@ -701,6 +921,9 @@ class Stage1Trainer:
             for k, p_ in own.items():
                 p_.copy_(model_sd[k])
         bump_weight_generation(self.model)
+        return self._restore_record(st, restore_hyperparameters)
+
+    def _restore_record(self, st, restore_hyperparameters: bool) -> int:
         self.step_count = int(st["step_count"])
         if restore_hyperparameters:
             self.lr, self.wd, self.eps = float(st["lr"]), float(st["weight_decay"]), float(st["eps"])
@@ -708,6 +931,51 @@ class Stage1Trainer:
             self.lr_scheduler = st.get("lr_scheduler", self.lr_scheduler)
             self.lr_warmup_steps = int(st.get("lr_warmup_steps", self.lr_warmup_steps))
         return int(st["global_step"])
+
+    # LoRA mode: peft's adapter directory (adapter_model.safetensors + adapter_config.json; layout written from knowledge of
+    # peft's format, parity unpinned: DESIGN.md §6a) next to this trainer's own optimizer.safetensors / trainer_state.json
+    def _save_lora(self, path: str, step: int):
+        import json
+        import os
+        from safetensors.torch import save_file
+        from .lora import adapter_config
+        os.makedirs(path, exist_ok=True)
+        save_file({k: v.detach().cpu().contiguous() for k, v in self.lora.items()}, os.path.join(path, "adapter_model.safetensors"))
+        with open(os.path.join(path, "adapter_config.json"), "w") as f:
+            json.dump(adapter_config(self.lora_rank, self.lora_alpha, self.lora_targets), f, indent=2)
+        save_file({"lora_master": self.lora_master.cpu(), "lora_m": self.lora_m.cpu(), "lora_v": self.lora_v.cpu()},
+                  os.path.join(path, "optimizer.safetensors"))
+        with open(os.path.join(path, "trainer_state.json"), "w") as f:
+            json.dump({"step_count": self.step_count, "global_step": step, "lr": self.lr, "weight_decay": self.wd,
+                       "betas": list(self.betas), "eps": self.eps, "lr_scheduler": self.lr_scheduler,
+                       "lr_warmup_steps": self.lr_warmup_steps,
+                       "lora": {"r": self.lora_rank, "rp": self.lora_rp, "lora_alpha": self.lora_alpha,
+                                "target_modules": list(self.lora_targets), "numel": self._lora_numel}}, f)
+
+    def _load_lora(self, path: str, st):
+        import os
+        from safetensors.torch import load_file
+        from .lora import load_adapter
+        rec = st["lora"]
+        mine = {"r": self.lora_rank, "rp": self.lora_rp, "target_modules": list(self.lora_targets), "numel": self._lora_numel}
+        diff = {k: (rec.get(k), v) for k, v in mine.items() if rec.get(k) != v}
+        if diff:
+            raise VgptError(f"{path}: checkpoint does not match this trainer's adapters (checkpoint, trainer): {diff}")
+        cfg, tensors = load_adapter(path)
+        opt = load_file(os.path.join(path, "optimizer.safetensors"))
+        problems = [f"adapter tensor {k} missing" for k in self.lora if k not in tensors]
+        problems += [f"adapter tensor {k}: shape {tuple(tensors[k].shape)} != {tuple(v.shape)}" for k, v in self.lora.items()
+                     if k in tensors and tensors[k].shape != v.shape]
+        problems += [f"optimizer tensor {k} missing or mis-sized" for k in ("lora_master", "lora_m", "lora_v")
+                     if k not in opt or opt[k].numel() != self._lora_numel]
+        if problems:
+            raise VgptError(f"{path}: checkpoint does not match this trainer: " + "; ".join(problems[:8]))
+        for k, v in self.lora.items():
+            v.copy_(tensors[k])
+        if not self.forward_only:
+            self.lora_master.copy_(opt["lora_master"]); self.lora_m.copy_(opt["lora_m"]); self.lora_v.copy_(opt["lora_v"])
+        self.lora_alpha = float(cfg["lora_alpha"])
+        self.lora_scale = self.lora_alpha / self.lora_rank
 
     def auto_resume(self, results_dir: str) -> Optional[int]:
         """Load the checkpoint-{N} with the largest N under results_dir, if any (train...stage1.py:304-315)."""
