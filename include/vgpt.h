@@ -112,6 +112,16 @@ int vgpt_gemm_set_family(int family);
 /* The family vgpt_gemm_set_family last set (what decides, among other things, whether vgpt_gemm_norm_workspace_bytes is
  * non-zero); changes nothing. */
 int vgpt_gemm_get_family(void);
+/* What the last top-level GEMM call (vgpt_gemm_bf16, _tr, _rope, _rope_prenorm, _resid_rstd, vgpt_gated_mlp_act_fwd, _keep,
+ * _prenorm) launched, one record of 6 int32 per kernel launch, in launch order:
+ *   [0] kernel: 128 = the 128 x 128 kernel; 256 / 192 / 288 = the eight-wave 256 x 256 / 256 x 192 / 256 x 288 kernels;
+ *               8 / 6 / 9 = the four-wave kernel with 256- / 192- / 288-wide tiles (its NI)
+ *   [1] mode: 0 plain, 1 gated, 2 RoPE      [2] a_transposed      [3] w_transposed
+ *   [4] first row of the launch (non-zero: the remainder of a split plan)      [5] its row count
+ * Writes at most `cap` records to `out` (out may be null when cap is 0) and returns how many launches there were; a call that
+ * was refused, or had M == 0 (every entry point returns OK for it), leaves none.  A read-only record for tests: it decides nothing.  Like the family switch it is
+ * process-wide and not thread-safe: read it right after the call it is meant for. */
+int vgpt_gemm_last_launches(int32_t* out, int cap);
 
 /* RMSNorm folded into the GEMMs around it (a decoder layer's two Phi3RMSNorm calls, OmniGen/transformer.py:196-214 through
  * transformers' Phi3DecoderLayer: hidden = residual + attn(input_layernorm(hidden)); hidden = residual +
@@ -130,7 +140,9 @@ int vgpt_gemm_get_family(void);
  *       caller before its first use (it holds arrival counters that every launch leaves at zero again) and may be shared by
  *       all such launches of one stream;
  *   vgpt_gemm_bf16_resid_rstd: C = A W^T + resid (as vgpt_gemm_bf16 with VGPT_EPI_RESID; C may be resid), and
- *       rstd_out[m] = rsqrt(mean_n C[m, n]^2 + eps) on the rounded values;
+ *       rstd_out[m] = rsqrt(mean_n C[m, n]^2 + eps) on the rounded values.  M == 0 returns OK and touches nothing.  It always runs the four-wave
+ *       kernel, so the strides that kernel cannot address are refused here (ldc, ldr < 2^21; (256 + 8) * lda and (N + 8) * ldw
+ *       elements below 2 GiB) where vgpt_gemm_bf16 would take the other family;
  *   vgpt_rms_rstd: the same statistic of a matrix x (M, H) no GEMM here produced;
  *   vgpt_fold_norm_gain: W_out (N, K) = bf16(W[n][k] * gain[k]);
  *   vgpt_gemm_bf16_rope_prenorm / vgpt_gated_mlp_act_fwd_prenorm: vgpt_gemm_bf16_rope / vgpt_gated_mlp_act_fwd on

@@ -27,7 +27,8 @@ def test_header_declares_the_expected_surface():
     syms = header_symbols()
     assert len(syms) >= 25
     for must in ("vgpt_gemm_bf16", "vgpt_attn_blockmask_fwd", "vgpt_rmsnorm_fwd", "vgpt_rope_qk_inplace",
-                 "vgpt_gated_mlp_act_fwd", "vgpt_euler_cfg_update", "vgpt_mask_tile_summary", "vgpt_last_error"):
+                 "vgpt_gated_mlp_act_fwd", "vgpt_euler_cfg_update", "vgpt_mask_tile_summary", "vgpt_last_error",
+                 "vgpt_gemm_last_launches"):
         assert must in syms
 
 

@@ -1442,6 +1442,24 @@ int cu_count() {
     return v;
 }
 
+// Record of what the last top-level GEMM call launched (vgpt_gemm_last_launches): one entry per kernel launch.  Every
+// top-level entry point clears it; launch_cfg / launch_w4_cfg append.  Process-global and not thread-safe, like g_family;
+// it records and decides nothing.
+struct LaunchRec {
+    int kernel;   // 128 / 256 / 192 / 288: eight-wave tile config (128: the 128 x 128 kernel); 6 / 8 / 9: four-wave NI
+    int mode, atr, wtr;
+    int row0, rows;
+};
+constexpr int kMaxLaunchRecs = 8;
+LaunchRec g_launch_recs[kMaxLaunchRecs];
+int g_n_launch_recs = 0;
+int g_launch_row0 = 0;   // first row of the launch about to be recorded (the remainder launch of a split plan)
+void launch_recs_clear() { g_n_launch_recs = 0; g_launch_row0 = 0; }
+void launch_recs_add(int kernel, int mode, bool atr, bool wtr, int rows) {
+    if (g_n_launch_recs < kMaxLaunchRecs) g_launch_recs[g_n_launch_recs] = {kernel, mode, (int)atr, (int)wtr, g_launch_row0, rows};
+    ++g_n_launch_recs;
+}
+
 template <int MODE, typename C, int PIPE, bool ATR = false, bool WTR = false>
 int launch_cfg(GemmArgs g, int64_t n_out, hipStream_t s, const char* name) {
     static bool attr_set = false;
@@ -1466,6 +1484,7 @@ int launch_cfg(GemmArgs g, int64_t n_out, hipStream_t s, const char* name) {
     hipLaunchKernelGGL((gemm_bf16_kernel<MODE, C, PIPE, ATR, WTR>), dim3(grid), dim3(C::THREADS),
                        C::LDS_BYTES + C::BM * 4, s, g);
     VGPT_CHECK_LAUNCH(name);
+    launch_recs_add(C::BM == 128 ? 128 : C::BN, MODE, ATR, WTR, g.M);
     return VGPT_OK;
 }
 
@@ -1540,6 +1559,7 @@ int launch_w4_cfg(GemmArgs g, int64_t n_out, hipStream_t s, const char* name) {
     g.tiles_n = (int)cdiv(n_out, MODE == MODE_GATED ? BN / 2 : BN);
     hipLaunchKernelGGL((gemm_w4_kernel<MODE, NI, WTR, ATR>), dim3(g.tiles_m * g.tiles_n), dim3(256), LDS, s, g);
     VGPT_CHECK_LAUNCH(name);
+    launch_recs_add(NI, MODE, ATR, WTR, g.M);
     return VGPT_OK;
 }
 
@@ -1708,6 +1728,7 @@ int launch(const GemmArgs& g, int64_t n_out, hipStream_t s, const char* name) {
     }
     int rc = big(g1);
     if (rc != VGPT_OK) return rc;
+    g_launch_row0 = (int)m1;
     return launch_cfg<MODE, Cfg128, 0, ATR, WTR>(g2, n_out, s, name);
 }
 
@@ -1727,6 +1748,18 @@ VGPT_EXPORT int vgpt_gemm_set_family(int family) {
 }
 
 VGPT_EXPORT int vgpt_gemm_get_family(void) { return g_family; }
+
+// The launches of the last top-level GEMM call, 6 int32 each (kernel, mode, a_transposed, w_transposed, first row, rows);
+// writes at most `cap` of them and returns how many there were
+VGPT_EXPORT int vgpt_gemm_last_launches(int32_t* out, int cap) {
+    const int n = g_n_launch_recs < kMaxLaunchRecs ? g_n_launch_recs : kMaxLaunchRecs;
+    for (int i = 0; out != nullptr && i < n && i < cap; ++i) {
+        const LaunchRec& r = g_launch_recs[i];
+        out[i * 6 + 0] = r.kernel; out[i * 6 + 1] = r.mode; out[i * 6 + 2] = r.atr;
+        out[i * 6 + 3] = r.wtr; out[i * 6 + 4] = r.row0; out[i * 6 + 5] = r.rows;
+    }
+    return g_n_launch_recs;
+}
 
 /* ---- RMSNorm folded into the GEMMs around it ---- */
 namespace {
@@ -1754,10 +1787,12 @@ VGPT_EXPORT int64_t vgpt_gemm_norm_workspace_bytes(int64_t M, int64_t N, int64_t
 VGPT_EXPORT int vgpt_gemm_bf16_resid_rstd(const void* A, const void* W, void* C, const void* resid, float* rstd_out, void* workspace,
                                           int64_t workspace_bytes, float eps, int64_t M, int64_t N, int64_t K, int64_t lda,
                                           int64_t ldw, int64_t ldc, int64_t ldr, void* stream) {
+    launch_recs_clear();
     VGPT_REQUIRE(A && W && C && resid && rstd_out && workspace, VGPT_ERR_INVALID, "vgpt_gemm_bf16_resid_rstd: null pointer");
-    VGPT_REQUIRE(M > 0 && N > 0 && K > 0 && K % BK == 0 && N % 4 == 0 && ldc % 4 == 0 && ldr % 4 == 0 && lda % 8 == 0 && ldw % 8 == 0 &&
+    VGPT_REQUIRE(M >= 0 && N > 0 && K > 0 && K % BK == 0 && N % 4 == 0 && ldc % 4 == 0 && ldr % 4 == 0 && lda % 8 == 0 && ldw % 8 == 0 &&
                      aligned16(A) && aligned16(W) && ((uintptr_t)C & 7) == 0 && ((uintptr_t)resid & 7) == 0 && eps >= 0.f,
                  VGPT_ERR_UNSUPPORTED, "vgpt_gemm_bf16_resid_rstd: shape / alignment as vgpt_gemm_bf16");
+    if (M == 0) return VGPT_OK;
     const int64_t need = vgpt_gemm_norm_workspace_bytes(M, N, K);
     VGPT_REQUIRE(need > 0, VGPT_ERR_UNSUPPORTED,
                  "vgpt_gemm_bf16_resid_rstd: not a shape of the four-wave kernel (vgpt_gemm_norm_workspace_bytes)");
@@ -1773,12 +1808,17 @@ VGPT_EXPORT int vgpt_gemm_bf16_resid_rstd(const void* A, const void* W, void* C,
     g.ssq_cnt = (int*)workspace;
     g.ssq_out = (float*)((char*)workspace + norm_cnt_bytes(M));
     g.rstd_out = rstd_out; g.nrm_ld = M; g.nrm_eps = eps; g.nrm_inv_h = 1.0f / (float)N;
+    // the workspace size was decided on dense strides; the launch uses the caller's
+    VGPT_REQUIRE(w4_ok<MODE_PLAIN>(g, N), VGPT_ERR_UNSUPPORTED,
+                 "vgpt_gemm_bf16_resid_rstd: row strides beyond the four-wave kernel's offset range (ldc, ldr < 2^21; 264 rows of A "
+                 "and N + 8 rows of W below 2 GiB)");
     return launch_w4<MODE_PLAIN>(g, N, (hipStream_t)stream, "vgpt_gemm_bf16_resid_rstd");
 }
 
 VGPT_EXPORT int vgpt_gemm_bf16(const void* A, const void* W, void* C, const void* extra, int64_t M,
                                int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc,
                                int64_t ldr, int epilogue, void* stream) {
+    launch_recs_clear();
     VGPT_REQUIRE(A && W && C, VGPT_ERR_INVALID, "vgpt_gemm_bf16: null pointer");
     VGPT_REQUIRE(M >= 0 && N > 0 && K > 0, VGPT_ERR_INVALID, "vgpt_gemm_bf16: bad shape");
     VGPT_REQUIRE(epilogue == VGPT_EPI_NONE || epilogue == VGPT_EPI_RESID || epilogue == VGPT_EPI_BIAS,
@@ -1808,6 +1848,7 @@ VGPT_EXPORT int vgpt_gemm_bf16(const void* A, const void* W, void* C, const void
 VGPT_EXPORT int vgpt_gemm_bf16_tr(const void* A, const void* W, void* C, const void* extra, int64_t M, int64_t N, int64_t K,
                                   int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int epilogue, int a_transposed,
                                   int w_transposed, void* stream) {
+    launch_recs_clear();
     if (!a_transposed && !w_transposed)
         return vgpt_gemm_bf16(A, W, C, extra, M, N, K, lda, ldw, ldc, ldr, epilogue, stream);
     VGPT_REQUIRE(A && W && C, VGPT_ERR_INVALID, "vgpt_gemm_bf16_tr: null pointer");
@@ -1819,7 +1860,7 @@ VGPT_EXPORT int vgpt_gemm_bf16_tr(const void* A, const void* W, void* C, const v
                  "vgpt_gemm_bf16_tr: K=%ld must be a multiple of 64 unless both operands are transposed", (long)K);
     VGPT_REQUIRE(!a_transposed || w_transposed, VGPT_ERR_UNSUPPORTED,
                  "vgpt_gemm_bf16_tr: a transposed A needs a transposed W (dW = dY^T X)");
-    VGPT_REQUIRE(N % 8 == 0 && N >= 8 && (!a_transposed || (M % 8 == 0 && M >= 8)), VGPT_ERR_UNSUPPORTED,
+    VGPT_REQUIRE(N % 8 == 0 && N >= 8 && (!a_transposed || M == 0 || (M % 8 == 0 && M >= 8)), VGPT_ERR_UNSUPPORTED,
                  "vgpt_gemm_bf16_tr: the width of a transposed operand must be a multiple of 8");
     VGPT_REQUIRE(ldc % 4 == 0 && (epilogue != VGPT_EPI_RESID || ldr % 4 == 0), VGPT_ERR_UNSUPPORTED,
                  "vgpt_gemm_bf16_tr: ldc/ldr must be multiples of 4");
@@ -1847,12 +1888,14 @@ static int gated_mlp_impl(const void* A, const void* W_gate_up, void* out, void*
 VGPT_EXPORT int vgpt_gated_mlp_act_fwd(const void* A, const void* W_gate_up, void* out, int64_t M,
                                        int64_t I, int64_t K, int64_t lda, int64_t ldw, int64_t ldo,
                                        int act, void* stream) {
+    launch_recs_clear();
     return gated_mlp_impl(A, W_gate_up, out, nullptr, M, I, K, lda, ldw, ldo, 0, act, stream);
 }
 
 VGPT_EXPORT int vgpt_gated_mlp_act_fwd_keep(const void* A, const void* W_gate_up, void* out, void* gate_up_out, int64_t M,
                                             int64_t I, int64_t K, int64_t lda, int64_t ldw, int64_t ldo, int64_t ld_gu,
                                             int act, void* stream) {
+    launch_recs_clear();
     VGPT_REQUIRE(gate_up_out && ld_gu >= 2 * I && ld_gu % 4 == 0 && ((uintptr_t)gate_up_out & 7) == 0, VGPT_ERR_INVALID,
                  "vgpt_gated_mlp_act_fwd_keep: gate_up_out must be an 8-byte aligned (M, >= 2I) buffer, ld_gu a multiple of 4");
     return gated_mlp_impl(A, W_gate_up, out, gate_up_out, M, I, K, lda, ldw, ldo, ld_gu, act, stream);
@@ -1860,6 +1903,7 @@ VGPT_EXPORT int vgpt_gated_mlp_act_fwd_keep(const void* A, const void* W_gate_up
 
 VGPT_EXPORT int vgpt_gated_mlp_act_fwd_prenorm(const void* A, const void* W_gate_up, void* out, const float* rstd, int64_t M,
                                                int64_t I, int64_t K, int64_t lda, int64_t ldw, int64_t ldo, int act, void* stream) {
+    launch_recs_clear();
     VGPT_REQUIRE(rstd, VGPT_ERR_INVALID, "vgpt_gated_mlp_act_fwd_prenorm: needs the rows' 1 / rms");
     return gated_mlp_impl(A, W_gate_up, out, nullptr, M, I, K, lda, ldw, ldo, 0, act, stream, rstd);
 }
@@ -1922,12 +1966,14 @@ static int gemm_rope_impl(const void* A, const void* W, void* C, const float* co
 VGPT_EXPORT int vgpt_gemm_bf16_rope(const void* A, const void* W, void* C, const float* cos_t, const float* sin_t,
                                     int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc,
                                     int n_rot_heads, int head_dim, void* stream) {
+    launch_recs_clear();
     return gemm_rope_impl(A, W, C, cos_t, sin_t, M, N, K, lda, ldw, ldc, n_rot_heads, head_dim, stream, nullptr);
 }
 
 VGPT_EXPORT int vgpt_gemm_bf16_rope_prenorm(const void* A, const void* W, void* C, const float* cos_t, const float* sin_t,
                                             const float* rstd, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                                             int64_t ldc, int n_rot_heads, int head_dim, void* stream) {
+    launch_recs_clear();
     VGPT_REQUIRE(rstd, VGPT_ERR_INVALID, "vgpt_gemm_bf16_rope_prenorm: needs the rows' 1 / rms");
     return gemm_rope_impl(A, W, C, cos_t, sin_t, M, N, K, lda, ldw, ldc, n_rot_heads, head_dim, stream, rstd);
 }
