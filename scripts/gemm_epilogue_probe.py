@@ -1,6 +1,6 @@
 """Developer probe (GPU): the step's four GEMMs at M = 4096 with a rotating set of weight matrices (so that weights come
-from HBM as in the sampler step, not from the Infinity Cache of a same-weights loop).  Run once with the product library
-and once with VGPT_LIB=video-gpt_amd/libvgpt_hip_g4.so (make gemm-debug-4: no epilogue) to see what the epilogue costs."""
+from HBM as in the sampler step, not from the Infinity Cache of a same-weights loop).  VGPT_LIB selects another build of the
+library for a same-box A/B run."""
 import importlib, sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 importlib.import_module("video-gpt_amd")

@@ -4,7 +4,7 @@ element by element, called through the C ABI (_lib.call) so that every row strid
   * WHICH KERNEL RAN is asserted by every case through vgpt_gemm_last_launches (kernel id, mode, transposed flags, first row,
     rows of every launch).  The grids below were found with that query on a 256-CU MI355X; when the launch plan moves, the
     case fails instead of quietly testing another kernel.  Kernel ids: 128 = the 128 x 128 kernel, 256 / 192 / 288 = the
-    eight-wave 256-row kernels (loops PIPE 1, 1, 5), 8 / 6 / 9 = the four-wave kernel's NI (256- / 192- / 288-wide tiles);
+    eight-wave 256-row kernels (four-, four- and six-phase loops), 8 / 6 / 9 = the four-wave kernel's NI (256- / 192- / 288-wide tiles);
     "split" = eight-wave 256 x 256 on the first 4096 rows, the 128 x 128 kernel on the rest through offset pointers.
   * GUARD BANDS AND STRIDES: every operand lives in an allocation with 256 guard rows before and after it (two in the one
     case whose output rows are 4 MiB each, test_output_stride_at_the_four_wave_limit) and a row stride
@@ -21,11 +21,12 @@ element by element, called through the C ABI (_lib.call) so that every row strid
     the stored [gate | up] of the keep form, dX / dW, and RoPE with tables of 0 and +-1 (quarter turns); the activations and
     a general rotation do not.  A global rel-L2 (4e-3, as tests/test_ops_gpu.py) stands next to every element-wise bound.
 
-Measured on one MI355X: the 85 cases take 4.0 s together (the slowest, the first to touch the device, 1.0 s; the others 0.03
+Measured on one MI355X: the 85 value cases take 4.0 s together (the slowest, the first to touch the device, 1.0 s; the others 0.03
 to 0.25 s).  Worst |err| / bound per group (MEASURE lines): plain epilogues 0.993 over 68 cases, dX 0.983, dW 0.993, stored
 [gate | up] 0.991, activations 0.999, RoPE 1.000 (0.9995: the bound is reached where the first rounding flips), rstd 2.2e-7
 relative under 3e-6.  The ratios sit just under 1 by construction: ulp / 2 is what a correct final rounding reaches among 16 M
-outputs, and the accumulation term e is 1e-5 .. 1e-4 of it at these K -- there is no slack for a wrong element to hide in."""
+outputs, and the accumulation term e is 1e-5 .. 1e-4 of it at these K -- there is no slack for a wrong element to hide in.
+test_launch_decision_at_workload_shapes adds 22 calls that check the launch record alone, 2.3 s together."""
 import contextlib
 import ctypes
 import importlib
@@ -629,3 +630,58 @@ def test_resid_rstd(L, kernel, M, N, K):
         L.call("vgpt_gemm_bf16_resid_rstd", A.ptr, W.ptr, C.ptr, xptr, Rs.ptr, ws.ptr, need - 1, eps, M, N, K, A.ld, W.ld, C.ld, ldr,
                None)
     assert _launches(L) == []
+
+
+# ============================================================================================================
+# the launch decision at the workload's own shapes
+# ============================================================================================================
+# id: (entry, M, N or I, K, expected records in family 0, in family 1).  The small-shape cases above reach every kernel; these
+# reach what only the workload's sizes do: round splits of the eight-wave plan (7740 rows), the 288-wide choice (qkv_proj), the
+# 192 / 256 choice of both families' cost models at 48 and 128 k-tiles, the 128-tile threshold.  The records are those of
+# commit 04b49a6 on a 256-CU MI355X.  dW = dY^T X is called as the trainer calls it, with the 7740 tokens as the reduction
+# length (a transposed A's width, here the weight's rows, must be a multiple of 8, which 7740 is not).
+WORKLOAD_LAUNCHES = {
+    "qkv_rope": ("rope", 4096, 9216, 3072, [(9, ROPE, 0, 0, 0, 4096)], [(288, ROPE, 0, 0, 0, 4096)]),
+    "o_proj_resid": ("resid", 4096, 3072, 3072, [(6, PLAIN, 0, 0, 0, 4096)], [(192, PLAIN, 0, 0, 0, 4096)]),
+    "gate_up_gated": ("gated", 4096, 8192, 3072, [(8, GATED, 0, 0, 0, 4096)], [(256, GATED, 0, 0, 0, 4096)]),
+    "down_proj": ("resid", 4096, 3072, 8192, [(6, PLAIN, 0, 0, 0, 4096)], [(192, PLAIN, 0, 0, 0, 4096)]),
+    "nt_7740x9216": ("nt", 7740, 9216, 3072, [(8, PLAIN, 0, 0, 0, 7740)],
+                     [(256, PLAIN, 0, 0, 0, 7168), (128, PLAIN, 0, 0, 7168, 572)]),
+    "nt_7740x3072": ("nt", 7740, 3072, 3072, [(6, PLAIN, 0, 0, 0, 7740)],
+                     [(256, PLAIN, 0, 0, 0, 5376), (128, PLAIN, 0, 0, 5376, 2364)]),
+    "dx_7740x9216": ("dx", 7740, 9216, 3072, [(8, PLAIN, 0, 1, 0, 7740)],
+                     [(256, PLAIN, 0, 1, 0, 7168), (128, PLAIN, 0, 1, 7168, 572)]),
+    "dx_7740x3072": ("dx", 7740, 3072, 3072, [(6, PLAIN, 0, 1, 0, 7740)],
+                     [(256, PLAIN, 0, 1, 0, 5376), (128, PLAIN, 0, 1, 5376, 2364)]),
+    "dw_9216x3072_over_7740": ("dw", 9216, 3072, 7740, [(8, PLAIN, 1, 1, 0, 9216)], [(256, PLAIN, 1, 1, 0, 9216)]),
+    "dw_3072x3072_over_7740": ("dw", 3072, 3072, 7740, [(6, PLAIN, 1, 1, 0, 3072)], [(256, PLAIN, 1, 1, 0, 3072)]),
+    "nt_below_the_128_tile_threshold": ("nt", 544, 3072, 3072, [(128, PLAIN, 0, 0, 0, 544)], [(128, PLAIN, 0, 0, 0, 544)]),
+}
+
+
+@pytest.mark.parametrize("fam", [0, 1])
+@pytest.mark.parametrize("cid", list(WORKLOAD_LAUNCHES))
+def test_launch_decision_at_workload_shapes(L, cid, fam):
+    """One call on dense zero operands; only the launch record is under test (the kernels are pinned above)."""
+    entry, M, N, K, *expect = WORKLOAD_LAUNCHES[cid]
+    z = lambda *shape, dtype=BF: torch.zeros(shape, dtype=dtype, device=DEV)
+    with _family(L, fam):
+        if entry == "rope":
+            hd, n_rot = 96, 64
+            a, w, c, cs, sn = z(M, K), z(N, K), z(M, N), z(M, hd // 2, dtype=F32), z(M, hd // 2, dtype=F32)
+            L.call("vgpt_gemm_bf16_rope", a.data_ptr(), w.data_ptr(), c.data_ptr(), cs.data_ptr(), sn.data_ptr(), M, N, K, K, K, N,
+                   n_rot, hd, None)
+        elif entry == "gated":
+            a, w, c = z(M, K), z(2 * N, K), z(M, N)
+            L.call("vgpt_gated_mlp_act_fwd", a.data_ptr(), w.data_ptr(), c.data_ptr(), M, N, K, K, K, N, 0, None)
+        elif entry in ("nt", "resid"):
+            a, w, c = z(M, K), z(N, K), z(M, N)
+            epi, xptr, ldr = (EPI_RESID, c.data_ptr(), N) if entry == "resid" else (EPI_NONE, None, 0)
+            L.call("vgpt_gemm_bf16", a.data_ptr(), w.data_ptr(), c.data_ptr(), xptr, M, N, K, K, K, N, ldr, epi, None)
+        else:
+            atr = int(entry == "dw")
+            a, w, c = (z(K, M) if atr else z(M, K)), z(K, N), z(M, N)
+            L.call("vgpt_gemm_bf16_tr", a.data_ptr(), w.data_ptr(), c.data_ptr(), None, M, N, K, a.shape[1], N, N, 0, EPI_NONE, atr, 1,
+                   None)
+        _ran(L, expect[fam], f"{cid} family {fam}")
+    torch.cuda.synchronize()

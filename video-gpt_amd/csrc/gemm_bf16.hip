@@ -24,58 +24,21 @@
 
 #include "common.h"
 
-#ifndef VGPT_GEMM_SETPRIO
-#define VGPT_GEMM_SETPRIO 0
-#endif
-// Diagnostics build (make gemm-debug-N, results are garbage): 1 = skip the LDS-DMA staging, 2 = skip the LDS fragment
-// reads, 3 = both, 4 = skip the epilogue, 16 = no wait for the LDS-DMA (what the per-tile drain costs).  A COMPILE-time switch: as a run-time flag the skipped reads became conditional, and at the join
-// hipcc's s_waitcnt insertion assumes the shorter path — every MFMA phase then waited for the fragment reads issued
-// right in front of it (lgkmcnt(3..0) instead of (7..4)), exposing the LDS latency twice per k-tile.
-#ifndef VGPT_GEMM_DEBUG_BUILD
-#define VGPT_GEMM_DEBUG_BUILD 0
-#endif
-
-// EXPERIMENT switch (make gemm-variant-VGPT_GEMM_STORE_WT): the epilogue's 8-byte output stores as write-through
-// (`sc0 sc1`: the line is not kept dirty in the XCD's L2), to see what the write-back of a GEMM's dirty output lines costs
-// at the kernel boundary behind it (MI355X_MICROARCH.md, price list row `boundary`: + B / 6 TB/s for B dirty bytes).
-// Measured in round 3: 35.3 ms per sampler step against 32.0 (o_proj 97 vs 72 us, qkv 242 vs 205): the consumer kernel
-// finds its input in neither L2 nor -- apparently -- as readily in the Infinity Cache; the plain stores stay.  VAL=2 (`nt`,
-// non-temporal) is worse still: gate_up 366 vs 326 us, qkv + RoPE 303 vs 201 us, 35.2 vs 30.8 ms per step -- the epilogue's
-// stores are 8 bytes per lane and it is the write-back L2 that merges them into whole lines.
-// Also measured and removed (round 3): software prefetch into the XCD's L2 -- wave 0 / 1 of every workgroup touching one dword
-// per 128-byte line of a 1/4 (A) / 1/8 (W) slice of the k-pieces three k-tiles ahead, so that the first of the 4 / 8
-// workgroups of an XCD that want a piece no longer misses L2 (12 of 64 piece fetches per k-tile do: the 16-19 % beyond-L2
-// fills of the counters).  Same box: 34.0 ms per sampler step against 33.35 / 33.43, 8192^3 1254 vs 1306 TFLOP/s: the extra
-// vector-memory instructions cost the loop more than the Infinity-Cache-served fills do.
-#ifndef VGPT_GEMM_STORE_WT
-#define VGPT_GEMM_STORE_WT 0
-#endif
-
 namespace {
 
-__device__ __forceinline__ void store_out4(bf16* p, bf16x4 v) {
-#if VGPT_GEMM_STORE_WT == 1
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-    const u32x2_t d = __builtin_bit_cast(u32x2_t, v);
-    asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(d) : "memory");
-#elif VGPT_GEMM_STORE_WT == 2   // non-temporal: the output streams through the L2 instead of displacing the operand panels
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-    const u32x2_t d = __builtin_bit_cast(u32x2_t, v);
-    asm volatile("global_store_dwordx2 %0, %1, off nt" ::"v"(p), "v"(d) : "memory");
-#else
-    *reinterpret_cast<bf16x4*>(p) = v;
-#endif
-}
+__device__ __forceinline__ void store_out4(bf16* p, bf16x4 v) { *reinterpret_cast<bf16x4*>(p) = v; }
 
 constexpr int BK = 64;
-constexpr int kDebug = VGPT_GEMM_DEBUG_BUILD;
 
-// Tile configuration: BM x BN block tile, WM x WN waves, every wave owns (BM/WM) x (BN/WN).
+// Main loop of a tile configuration: the simple double-buffered loop, or the software pipeline in four / six phases
+enum { LOOP_SIMPLE = 0, LOOP_4PHASE = 1, LOOP_6PHASE = 2 };
+
+// Tile configuration: BM x BN block tile, WM x WN waves, every wave owns (BM/WM) x (BN/WN), and the main loop written for it.
 //   Cfg128: 128x128, 2x2 waves of 64x64   (64 KiB LDS, 2 blocks/CU)  — small problems
 //   Cfg256: 256x256, 2x4 waves of 128x64  (128 KiB LDS, 1 block/CU)  — halves the L2->LDS bytes per FLOP
-template <int BM_, int BN_, int WM_, int WN_>
+template <int BM_, int BN_, int WM_, int WN_, int LOOP_>
 struct TileCfg {
-    static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
+    static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, LOOP = LOOP_;
     static constexpr int NWAVES = WM * WN, THREADS = NWAVES * 64;
     static constexpr int MI = BM / WM / 16, NI = BN / WN / 16;  // 16x16 sub-tiles per wave
     static constexpr int A_BYTES = BM * BK * 2, W_BYTES = BN * BK * 2;
@@ -86,22 +49,20 @@ struct TileCfg {
     static constexpr bool W_EVEN = W_TOTAL % NWAVES == 0;
     static constexpr int A_SLABS = BM / 8 / NWAVES, W_SLABS = (W_TOTAL + NWAVES - 1) / NWAVES;
     static_assert(BM % (8 * NWAVES) == 0 && BN % 8 == 0, "slabs must divide over waves");
+    static_assert(LOOP != LOOP_4PHASE || (MI == 8 && (NI == 4 || NI == 3)), "four-phase loop: 2x4-wave tiles of 128 x 64 / 128 x 48");
+    static_assert(LOOP != LOOP_6PHASE || (MI == 4 && NI == 9), "six-phase loop: 4x2-wave tiles of 64 x 144");
     static __device__ __host__ constexpr int w_slab(int wave, int i) { return W_EVEN ? wave * W_SLABS + i : i * NWAVES + wave; }
 };
-using Cfg128 = TileCfg<128, 128, 2, 2>;
-using Cfg256 = TileCfg<256, 256, 2, 4>;
+using Cfg128 = TileCfg<128, 128, 2, 2, LOOP_SIMPLE>;
+using Cfg256 = TileCfg<256, 256, 2, 4, LOOP_4PHASE>;
 // 256 x 192: same loop with 3 instead of 4 n sub-tiles per wave (wave tile 128 x 48).  For problems whose 256-tile
 // grid fills the last round badly: M = 4096 rows x N = 3072 is 192 tiles of 256 x 256 (a 75 % round) but exactly 256
 // tiles of 256 x 192; x N = 9216 it is 2.25 rounds against 3 full rounds of 0.75-size tiles.
-using Cfg192 = TileCfg<256, 192, 2, 4>;
-// 256 x 288, 4 x 2 waves of 64 x 144 (MI = 4, NI = 9), six-phase loop (PIPE == 5): N = 9216 (qkv_proj of the Phi-3-mini-class
+using Cfg192 = TileCfg<256, 192, 2, 4, LOOP_4PHASE>;
+// 256 x 288, 4 x 2 waves of 64 x 144 (MI = 4, NI = 9), six-phase loop: N = 9216 (qkv_proj of the Phi-3-mini-class
 // denoiser) is 32 such tiles, so M = 4096 rows make exactly two rounds of 256 workgroups where 256-wide tiles make 2.25 and
 // 192-wide ones three (and a 192-wide tile's k-step takes as long as a 256-wide one's: the loop is not bound by its MFMAs)
-using Cfg288 = TileCfg<256, 288, 4, 2>;
-// 256 x 256 with FOUR waves of 128 x 128 (MI = NI = 8: 256 accumulator registers, one wave per SIMD, 512-register budget)
-// and the register-staged, fragment-streaming loop PIPE == 6: every fragment feeds 8 MFMAs (a third fewer LDS bytes per
-// FLOP than the 128 x 64 wave tile) and no instruction of the loop is an LDS-DMA.  EXPERIMENT: VGPT_GEMM_TILE=512.
-using Cfg256w4 = TileCfg<256, 256, 2, 2>;
+using Cfg288 = TileCfg<256, 288, 4, 2, LOOP_6PHASE>;
 
 enum { MODE_PLAIN = 0, MODE_GATED = 1, MODE_ROPE = 2 };
 
@@ -201,16 +162,33 @@ __device__ __forceinline__ int rope_col_of_slot(int gs, int rope_cols, int head_
     return (u / per) * head_dim + (u % per) * 8 + (w & 7) + ((w & 8) ? (head_dim >> 1) : 0);
 }
 
-constexpr bool getenv_prio = VGPT_GEMM_SETPRIO;
+// Tile order of both kernels: XCD-aware remap of the workgroup id (bijective), then grouped along m, so that workgroups
+// sharing an XCD's L2 work on neighbouring tiles.  Returns the tile's row (tm) and column (tn) index.
+__device__ __forceinline__ void tile_of_block(int bid, int tiles_m, int tiles_n, int& tm, int& tn) {
+    const int nwg = tiles_m * tiles_n;
+    {
+        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    }
+    constexpr int GROUP = 8;
+    const int in_group = GROUP * tiles_n;
+    const int group_id = bid / in_group;
+    const int first_m = group_id * GROUP;
+    const int gsz = min(tiles_m - first_m, GROUP);
+    tm = first_m + (bid % in_group) % gsz;
+    tn = (bid % in_group) / gsz;
+}
 
 // ATR / WTR: the operand is stored with the reduction index as its ROW index (A as [K][M], W as [K][N]) -- the dX and
 // dW products of the backward (dX = dY W, dW = dY^T X) without materialising a transpose.  Such a tile is staged in
 // its natural [64 reduction rows][256 columns] layout and its MFMA fragments come from ds_read_b64_tr_b16; the
 // 32-byte units of a row are XOR-swizzled with ((row>>3)&1)<<2 | (row&3) (on the DMA source address and on the
 // read) so that the 8 rows x 32 B a half-wave reads transposed hit 64 different banks.
-template <int MODE, typename C, int PIPE, bool ATR = false, bool WTR = false>
+// The main loop is the tile configuration's (C::LOOP).
+template <int MODE, typename C, bool ATR = false, bool WTR = false>
 __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
     static_assert(!(ATR || WTR) || MODE == MODE_PLAIN, "transposed operands: plain kernel only");
+    static_assert(C::LOOP != LOOP_6PHASE || (!ATR && !WTR), "six-phase loop: NT operands");
     constexpr bool ROPE = MODE == MODE_ROPE;
     constexpr int BM = C::BM, BN = C::BN, MI = C::MI, NI = C::NI;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -218,11 +196,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // ---- tile order: XCD-aware remap (bijective), then grouped along m.  A workgroup walks the virtual tile ids
-    //      blockIdx.x, blockIdx.x + gridDim.x, ... (persistent launch: gridDim.x = one round of the chip; a plain launch
-    //      has gridDim.x = number of tiles and the walk ends after one).  gridDim.x % 8 == 0 or a single round, so a
-    //      workgroup's tiles keep `vt & 7`, the XCD the remap assumes. ----
-    const int nwg = g.tiles_m * g.tiles_n;
     // ---- staging addresses: wave w stages its share of 8-row slabs of both tiles ----
     const int srow = lane >> 3;            // row inside the 8-row slab
     const int schunk = (lane & 7) ^ srow;  // source 16-B chunk (XOR swizzle)
@@ -246,28 +219,16 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
     int m0 = 0, n0 = 0;
     const char* a_org = nullptr;
     const char* w_org = nullptr;
-    auto set_tile = [&](int vt, bool remap = true) {
-        int bid = vt;
-        if (remap) {
-            const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-            bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-        }
-        constexpr int GROUP = 8;
-        const int in_group = GROUP * g.tiles_n;
-        const int group_id = bid / in_group;
-        const int first_m = group_id * GROUP;
-        const int gsz = min(g.tiles_m - first_m, GROUP);
-        const int tm = first_m + (bid % in_group) % gsz;
-        const int tn = (bid % in_group) / gsz;
+    // origins and staging offsets of tile vt
+    auto set_tile = [&](int vt) {
+        int tm, tn;
+        tile_of_block(vt, g.tiles_m, g.tiles_n, tm, tn);
         m0 = tm * BM;
         n0 = tn * (MODE == MODE_GATED ? BN / 2 : BN);
-        // diagnostics bit 64 (results are garbage): every workgroup reads the operands of tile (0, 0) -- an L2-resident operand
-        // stream under the product's instruction stream, to tell memory latency under load from issue / clock limits
-        const int m0l = (kDebug & 64) ? 0 : m0, n0l = (kDebug & 64) ? 0 : n0;
-        a_org = reinterpret_cast<const char*>(ATR ? g.A + m0l : g.A + (int64_t)m0l * g.lda);
-        if constexpr (WTR) w_org = reinterpret_cast<const char*>(g.W + n0l);
+        a_org = reinterpret_cast<const char*>(ATR ? g.A + m0 : g.A + (int64_t)m0 * g.lda);
+        if constexpr (WTR) w_org = reinterpret_cast<const char*>(g.W + n0);
         else if constexpr (MODE == MODE_GATED || ROPE) w_org = reinterpret_cast<const char*>(g.W);
-        else w_org = reinterpret_cast<const char*>(g.W + (int64_t)n0l * g.ldw);
+        else w_org = reinterpret_cast<const char*>(g.W + (int64_t)n0 * g.ldw);
 #pragma unroll
         for (int i = 0; i < C::A_SLABS; ++i) {
             if constexpr (ATR) {
@@ -313,7 +274,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
     char* sW = smem + 2 * C::A_BYTES;   // [2][W_BYTES]
 
     auto stage = [&](int buf, int kt) {
-        if constexpr (kDebug & 1) return;
 #pragma unroll
         for (int i = 0; i < C::A_SLABS; ++i)
             a_issue(i, kt, sA + buf * C::A_BYTES + (wave * C::A_SLABS + i) * 1024);
@@ -321,6 +281,19 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
         for (int i = 0; i < C::W_SLABS; ++i)
             if (C::W_EVEN || C::w_slab(wave, i) < C::W_TOTAL)
                 w_issue(i, kt, sW + buf * C::W_BYTES + C::w_slab(wave, i) * 1024);
+    };
+    // the pipelined loops issue a k-tile's DMA in two halves: the first half of the A slabs and W slabs [0, W_SLABS/2),
+    // then the rest
+    auto stage_half = [&](int buf, int kt, int half) {
+#pragma unroll
+        for (int i = 0; i < C::A_SLABS / 2; ++i) {
+            const int ii = half * (C::A_SLABS / 2) + i;
+            a_issue(ii, kt, sA + buf * C::A_BYTES + (wave * C::A_SLABS + ii) * 1024);
+        }
+#pragma unroll
+        for (int ii = 0; ii < C::W_SLABS; ++ii)
+            if ((ii >= C::W_SLABS / 2) == (half != 0) && (C::W_EVEN || C::w_slab(wave, ii) < C::W_TOTAL))
+                w_issue(ii, kt, sW + buf * C::W_BYTES + C::w_slab(wave, ii) * 1024);
     };
 
     // ---- fragment read addresses ----
@@ -333,22 +306,14 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
     const int sw = frow & 7;
 
     f32x4 acc[NI][MI];
-    f32x16 acc2[2][4];   // diagnostics flag 32 only
-    // folded RMSNorm (consumer side): 1 / rms of this tile's rows, in LDS behind the staging buffers
+    // folded RMSNorm (consumer side): 1 / rms of this tile's rows, in LDS behind the staging buffers; read in the epilogue,
+    // behind the k-loop's barriers
     float* rs_lds = reinterpret_cast<float*>(smem + C::LDS_BYTES);
     auto load_rstd = [&](int m_first) {
         if constexpr (MODE != MODE_PLAIN) {
             if (g.nrm_rstd != nullptr && tid < BM) rs_lds[tid] = m_first + tid < g.M ? g.nrm_rstd[m_first + tid] : 0.f;
         }
     };
-    if constexpr ((kDebug & 32) != 0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc2[i][j][e] = 0.f;
-    }
 
     // transposed image: lane (g4 = lane>>4, li = lane&15) of the 16-column sub-tile `unit` reads rows
     // 32 ks + 8 g4 + (li>>2) (+4 for the upper half) at columns 4 (li&3) .. +4 -> k = 8 g4 + j of column li
@@ -362,21 +327,21 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
     };
 
     const int nk = (g.K + BK - 1) / BK;  // a partial last k-tile exists only with transposed operands (zero rows)
-    // Persistent walk (PERSIST): when this workgroup has another tile, that tile's first k-tile is requested (LDS-DMA into
-    // staging buffer 0, free once every wave is past the last barrier of the k-loop) BEFORE the epilogue of the current one,
-    // so the fetch latency of a tile's prologue and the HBM write time of its predecessor's epilogue overlap instead of
-    // adding up (one workgroup per CU: nothing else overlaps them).  Not for MODE_ROPE, whose epilogue stages the cos / sin
-    // rows through the same LDS, nor for the experimental loops.
-    constexpr bool PERSIST = (PIPE == 0 || PIPE == 1) && !ROPE;
+    // Tile walk.  Every launch has one workgroup per tile (gridDim.x = number of tiles), so the walk ends after the first
+    // tile and `prefetched` is never set.  The walk's code -- a workgroup with another tile (blockIdx.x + gridDim.x, ...) would
+    // request that tile's first k-tile before the epilogue of the current one -- is what is left of the persistent launch
+    // (measured to gain nothing: DESIGN.md); it stays because without it hipcc compiles these kernels differently and the
+    // eight-wave family's sampler step measured 1 % slower (32.36 against 32.05 ms, alternating runs on one box).
+    // Not for MODE_ROPE, whose epilogue stages the cos / sin rows through the same LDS, nor for the six-phase loop.
+    constexpr bool PERSIST = (C::LOOP == LOOP_SIMPLE || C::LOOP == LOOP_4PHASE) && !ROPE;
     bool prefetched = false;
-    const int kbeg = 0, kend = nk;
     for (;;) {
     load_rstd(m0);   // read in the epilogue, behind the k-loop's barriers
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
         for (int j = 0; j < MI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (PIPE == 0) {
+    if constexpr (C::LOOP == LOOP_SIMPLE) {
         // one barrier per k-tile: wait for tile kt, issue tile kt+1's DMA, compute tile kt
         if (!prefetched) stage(0, 0);
         for (int kt = 0; kt < nk; ++kt) {
@@ -407,12 +372,11 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[j], acc[i][j], 0, 0, 0);
             }
         }
-    } else if constexpr (PIPE == 5) {
+    } else if constexpr (C::LOOP == LOOP_6PHASE) {
         // 4x2-wave tiles of 64 x 144 (256 x 288): six phases of 12 MFMAs per k-tile -- (ks, third of the wave's nine n
         // sub-tiles) -- with the W fragments of phase p+1 (three reads) and the A fragments of the other k-step (four) in
         // flight under phase p's MFMAs, the per-tile barrier in front of the LAST phase and the next tile's first fragments
         // read behind it, the LDS-DMA in two halves as in the 4-phase loop.  200 accumulator + fragment registers.
-        static_assert(MI == 4 && NI == 9 && !ATR && !WTR, "six-phase loop: 4x2-wave tiles of 64 x 144, NT operands");
         bf16x8 Wt[2][3], Af2[2][4];
         auto ldW3 = [&](bf16x8(&dst)[3], int buf, int ks, int th) {
             const char* b = sW + buf * C::W_BYTES + w_base + th * (3 * 2048) + ((ks * 4 + fk) ^ sw) * 16;
@@ -432,17 +396,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
                 for (int j = 0; j < 4; ++j)
                     acc[TH * 3 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[j], acc[TH * 3 + i][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-        };
-        auto stage_half = [&](int buf, int kt, int half) {
-#pragma unroll
-            for (int i = 0; i < C::A_SLABS / 2; ++i) {
-                const int ii = half * (C::A_SLABS / 2) + i;
-                a_issue(ii, kt, sA + buf * C::A_BYTES + (wave * C::A_SLABS + ii) * 1024);
-            }
-#pragma unroll
-            for (int ii = 0; ii < C::W_SLABS; ++ii)
-                if ((ii >= C::W_SLABS / 2) == (half != 0) && (C::W_EVEN || C::w_slab(wave, ii) < C::W_TOTAL))
-                    w_issue(ii, kt, sW + buf * C::W_BYTES + C::w_slab(wave, ii) * 1024);
         };
         using T0 = std::integral_constant<int, 0>;
         using T1 = std::integral_constant<int, 1>;
@@ -483,20 +436,8 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
         // of phase p+1 are read from LDS while phase p's MFMAs run (two register sets), the next tile's
         // DMA is issued in two halves right after the per-tile barrier, and that barrier sits in front of
         // the LAST phase of a tile so the first fragments of tile kt+1 are prefetched under tile kt.
-        static_assert(MI == 8 && (NI == 4 || NI == 3), "pipelined loop is written for the 2x4-wave tiles of 128 x 64 / 128 x 48");
         bf16x8 Wf[2][NI], Af[2][4];
-        if constexpr ((kDebug & 2) != 0) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    Af[u][i] = bf16x8{(bf16)1.f, (bf16)0.5f, (bf16)-1.f, (bf16)2.f, (bf16)1.f, (bf16)0.5f, (bf16)-1.f, (bf16)2.f};
-#pragma unroll
-                for (int i = 0; i < NI; ++i) Wf[u][i] = Af[u][0];
-            }
-        }
         auto ldW = [&](bf16x8(&dst)[NI], int buf, int ks) {
-            if constexpr (kDebug & 2) return;
             if constexpr (WTR) {
 #pragma unroll
                 for (int i = 0; i < NI; ++i) dst[i] = ld_tr(sW + buf * C::W_BYTES, 2 * BN, ks, wn * NI + i);
@@ -507,7 +448,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
             }
         };
         auto ldA = [&](bf16x8(&dst)[4], int buf, int ks, int mh) {
-            if constexpr (kDebug & 2) return;
             if constexpr (ATR) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) dst[j] = ld_tr(sA + buf * C::A_BYTES, 2 * BM, ks, wm * 8 + mh * 4 + j);
@@ -517,56 +457,29 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
                 for (int j = 0; j < 4; ++j) dst[j] = *reinterpret_cast<const bf16x8*>(b + j * 2048);
             }
         };
-        // diagnostics flag 32 (with 4: results are garbage): the same fragments fed to 32x32x16 MFMAs, half as many for
-        // the same FLOPs and matrix-pipe time -- each holds the SIMD's vector issue for 8 of its 32 cycles, a 16x16x32
-        // for 8 of its 16 (MI355X_MICROARCH.md): what the loop would gain from the issue slots alone
         auto mma = [&](const bf16x8(&wf)[NI], const bf16x8(&af)[4], auto mh) {
             constexpr int MH = decltype(mh)::value;
-            if constexpr ((kDebug & 32) != 0 && NI == 4) {
-#pragma unroll
-                for (int i2 = 0; i2 < 2; ++i2)
-#pragma unroll
-                    for (int j2 = 0; j2 < 2; ++j2) {
-                        acc2[i2][MH * 2 + j2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[2 * i2], af[2 * j2], acc2[i2][MH * 2 + j2], 0, 0, 0);
-                        acc2[i2][MH * 2 + j2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[2 * i2 + 1], af[2 * j2 + 1], acc2[i2][MH * 2 + j2], 0, 0, 0);
-                    }
-                return;
-            }
-            if (getenv_prio) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int i = 0; i < NI; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     acc[i][MH * 4 + j] =
                         __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[j], acc[i][MH * 4 + j], 0, 0, 0);
-            if (getenv_prio) __builtin_amdgcn_s_setprio(0);
-        };
-        auto stage_half = [&](int buf, int kt, int half) {
-            if constexpr (kDebug & 1) return;
-#pragma unroll
-            for (int i = 0; i < C::A_SLABS / 2; ++i) {
-                const int ii = half * (C::A_SLABS / 2) + i;
-                a_issue(ii, kt, sA + buf * C::A_BYTES + (wave * C::A_SLABS + ii) * 1024);
-            }
-#pragma unroll
-            for (int ii = 0; ii < C::W_SLABS; ++ii)   // first half: slabs [0, W_SLABS/2), second: the rest
-                if ((ii >= C::W_SLABS / 2) == (half != 0))
-                    w_issue(ii, kt, sW + buf * C::W_BYTES + (wave * C::W_SLABS + ii) * 1024);
         };
         using H0 = std::integral_constant<int, 0>;
         using H1 = std::integral_constant<int, 1>;
 
-        if (!prefetched) stage(0, kbeg);
+        if (!prefetched) stage(0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (kend - kbeg > 1) stage(1, kbeg + 1);
+        if (nk > 1) stage(1, 1);
         ldW(Wf[0], 0, 0);
         ldA(Af[0], 0, 0, 0);
-        for (int kt = kbeg; kt < kend; ++kt) {
-            const int buf = (kt - kbeg) & 1;
+        for (int kt = 0; kt < nk; ++kt) {
+            const int buf = kt & 1;
             // phase 1: (ks0, m-half 0)
             ldA(Af[1], buf, 0, 1);
-            if (kt >= kbeg + 1 && kt + 1 < kend) stage_half(buf ^ 1, kt + 1, 1);
+            if (kt >= 1 && kt + 1 < nk) stage_half(buf ^ 1, kt + 1, 1);
             mma(Wf[0], Af[0], H0{});
             __builtin_amdgcn_sched_barrier(0);
             // phase 2: (ks0, m-half 1)
@@ -580,10 +493,10 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
             __builtin_amdgcn_sched_barrier(0);
             // phase 4: (ks1, m-half 1) — every wave has its last fragments of this tile in registers and
             // its share of tile kt+1 has landed: after the barrier buffer `buf` is free for tile kt+2
-            if constexpr ((kDebug & 16) == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // 16: timing without the drain
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            if (kt + 2 < kend) stage_half(buf, kt + 2, 0);
-            if (kt + 1 < kend) {
+            if (kt + 2 < nk) stage_half(buf, kt + 2, 0);
+            if (kt + 1 < nk) {
                 ldW(Wf[0], buf ^ 1, 0);
                 ldA(Af[0], buf ^ 1, 0, 0);
             }
@@ -592,13 +505,12 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
         }
     }
 
-
-    // ---- the tile whose accumulators are stored now; then (persistent walk) the next tile's first k-tile is requested ----
+    // ---- the tile whose accumulators are stored now; then (walk) the next tile's first k-tile is requested ----
     const int m0e = m0, n0e = n0;
     bool more = false;
     if constexpr (PERSIST) {
         const int vt_next = vt_cur + (int)gridDim.x;
-        more = vt_next < nwg;
+        more = vt_next < g.tiles_m * g.tiles_n;
         if (more) {
             __syncthreads();          // every wave has read its last fragments: both staging buffers are free
             vt_cur = vt_next;
@@ -606,23 +518,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
             stage(0, 0);
             prefetched = true;
         }
-    }
-    if constexpr ((kDebug & 4) != 0) {   // diagnostics: no epilogue (one store keeps the accumulators alive)
-        float sum = 0.f;
-        if constexpr ((kDebug & 32) != 0 && PIPE == 1) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) sum += acc2[i][j][e];
-        }
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int j = 0; j < MI; ++j) sum += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-        if (sum == 12345.678f) g.C[0] = f2bf(sum);
-        return;
     }
     // ---- epilogue: lane holds m = lane&15, n = (lane>>4)*4 + reg of each 16x16 sub-tile ----
     const int em = lane & 15, en = (lane >> 4) * 4;
@@ -720,88 +615,41 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
             }
         }
     } else {
-        // the activation is resolved OUTSIDE the unrolled loops (one instantiation per kind): with the switch inside, the
-        // 8 x 4 iterations of the 128 x 128 wave tile exceed the unroller's budget and the accumulators fall into scratch
-        auto gated_store = [&](auto actc, auto keepc) {
-            constexpr int ACT = decltype(actc)::value;
-            constexpr bool KEEP = decltype(keepc)::value;
 #pragma unroll
-            for (int j = 0; j < MI; ++j) {
-                const int m = m0e + wm * (MI * 16) + j * 16 + em;
-                if (m >= g.M) continue;
+        for (int j = 0; j < MI; ++j) {
+            const int m = m0e + wm * (MI * 16) + j * 16 + em;
+            if (m >= g.M) continue;
 #pragma unroll
-                for (int p = 0; p < NI / 2; ++p) {
-                    const int n = n0e + (wn * (NI / 2) + p) * 16 + en;  // output column
-                    if (n >= g.I) continue;
-                    const f32x4 gate = acc[2 * p][j], up = acc[2 * p + 1][j];
-                    bf16x4 o;
-                    if constexpr (KEEP) {
-                        bf16x4 gb, ub;
+            for (int p = 0; p < NI / 2; ++p) {
+                const int n = n0e + (wn * (NI / 2) + p) * 16 + en;  // output column
+                if (n >= g.I) continue;
+                f32x4 gate = acc[2 * p][j], up = acc[2 * p + 1][j];
+                if (g.nrm_rstd != nullptr) {
+                    const float rs = rs_lds[wm * (MI * 16) + j * 16 + em];
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            gb[t] = f2bf(gate[t]);
-                            ub[t] = f2bf(up[t]);
-                            o[t] = f2bf(act_apply(bf2f(gb[t]), ACT) * bf2f(ub[t]));
-                        }
-                        store_out4(g.gu_out + (int64_t)m * g.ld_gu + n, gb);
-                        store_out4(g.gu_out + (int64_t)m * g.ld_gu + g.I + n, ub);
-                    } else {
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) o[t] = f2bf(act_apply(gate[t], ACT) * up[t]);
-                    }
-                    store_out4(g.C + (int64_t)m * g.ldc + n, o);
+                    for (int t = 0; t < 4; ++t) { gate[t] *= rs; up[t] *= rs; }
                 }
-            }
-        };
-        using KT = std::true_type;
-        using KF = std::false_type;
-        if constexpr (PIPE != 6) {
-            // the 8-wave kernels (16 iterations) stay as they were measured: activation selected inside the loops
+                bf16x4 o;
+                if (g.gu_out) {
+                    bf16x4 gb, ub;
 #pragma unroll
-            for (int j = 0; j < MI; ++j) {
-                const int m = m0e + wm * (MI * 16) + j * 16 + em;
-                if (m >= g.M) continue;
-#pragma unroll
-                for (int p = 0; p < NI / 2; ++p) {
-                    const int n = n0e + (wn * (NI / 2) + p) * 16 + en;  // output column
-                    if (n >= g.I) continue;
-                    f32x4 gate = acc[2 * p][j], up = acc[2 * p + 1][j];
-                    if (g.nrm_rstd != nullptr) {
-                        const float rs = rs_lds[wm * (MI * 16) + j * 16 + em];
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) { gate[t] *= rs; up[t] *= rs; }
+                    for (int t = 0; t < 4; ++t) {
+                        gb[t] = f2bf(gate[t]);
+                        ub[t] = f2bf(up[t]);
+                        o[t] = f2bf(act_apply(bf2f(gb[t]), g.act) * bf2f(ub[t]));
                     }
-                    bf16x4 o;
-                    if (g.gu_out) {
-                        bf16x4 gb, ub;
+                    store_out4(g.gu_out + (int64_t)m * g.ld_gu + n, gb);
+                    store_out4(g.gu_out + (int64_t)m * g.ld_gu + g.I + n, ub);
+                } else {
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            gb[t] = f2bf(gate[t]);
-                            ub[t] = f2bf(up[t]);
-                            o[t] = f2bf(act_apply(bf2f(gb[t]), g.act) * bf2f(ub[t]));
-                        }
-                        store_out4(g.gu_out + (int64_t)m * g.ld_gu + n, gb);
-                        store_out4(g.gu_out + (int64_t)m * g.ld_gu + g.I + n, ub);
-                    } else {
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) o[t] = f2bf(act_apply(gate[t], g.act) * up[t]);
-                    }
-                    store_out4(g.C + (int64_t)m * g.ldc + n, o);
+                    for (int t = 0; t < 4; ++t) o[t] = f2bf(act_apply(gate[t], g.act) * up[t]);
                 }
+                store_out4(g.C + (int64_t)m * g.ldc + n, o);
             }
-        } else if (g.act == VGPT_ACT_SILU) {
-            if (g.gu_out) gated_store(std::integral_constant<int, VGPT_ACT_SILU>{}, KT{});
-            else gated_store(std::integral_constant<int, VGPT_ACT_SILU>{}, KF{});
-        } else if (g.act == VGPT_ACT_GELU) {
-            if (g.gu_out) gated_store(std::integral_constant<int, VGPT_ACT_GELU>{}, KT{});
-            else gated_store(std::integral_constant<int, VGPT_ACT_GELU>{}, KF{});
-        } else {
-            if (g.gu_out) gated_store(std::integral_constant<int, VGPT_ACT_GELU_TANH>{}, KT{});
-            else gated_store(std::integral_constant<int, VGPT_ACT_GELU_TANH>{}, KF{});
         }
     }
     if (!more) break;
-    }   // persistent walk
+    }   // tile walk
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -875,20 +723,8 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs g) {
     const uint32_t st_t0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
 
-    // ---- tile order: as gemm_bf16_kernel (XCD-aware remap, grouped along m) ----
-    const int nwg = g.tiles_m * g.tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    constexpr int GROUP = 8;
-    const int in_group = GROUP * g.tiles_n;
-    const int group_id = bid / in_group;
-    const int first_m = group_id * GROUP;
-    const int gsz = min(g.tiles_m - first_m, GROUP);
-    const int tm = first_m + (bid % in_group) % gsz;
-    const int tn = (bid % in_group) / gsz;
+    int tm, tn;
+    tile_of_block(blockIdx.x, g.tiles_m, g.tiles_n, tm, tn);
     const int m0 = tm * BM;
     const int n0 = tn * (MODE == MODE_GATED ? BN / 2 : BN);
     const int n_rows_w = (MODE == MODE_GATED) ? 2 * g.I : g.N;
@@ -1024,7 +860,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs g) {
                          : VGPT_W4_CLOBBERS_WTR);
         }
     } else if constexpr (NI == 9) {
-        // whole tiles only (launch_w4 checks): no per-lane row clamp, one SGPR offset per piece (lane p of `tab`: p < 8 the A
+        // whole tiles only (w4_cost288 checks): no per-lane row clamp, one SGPR offset per piece (lane p of `tab`: p < 8 the A
         // pieces, 8 + p the W pieces) on top of one per-lane offset per operand
         uint32_t tab;
         {
@@ -1093,7 +929,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs g) {
         // rows of the tile staged through the (now free) LDS
         const int half = g.head_dim >> 1;
         const int tab_bytes = (BM * half * 4 + 1023) & ~1023;
-        // (launch_w4 only takes head dims whose two tables fit: w4_ok)
+        // (the four-wave kernel only takes head dims whose two tables fit: w4_ok)
         {
             __syncthreads();
             const int64_t row0_bytes = (int64_t)m0 * half * 4;
@@ -1416,19 +1252,6 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs g) {
 #endif
 }
 
-// Persistent walk: OFF unless VGPT_GEMM_PERSIST=1.  Measured in round 3 on one box (bench.py, same process order): sampler
-// step 31.996 ms with it against 32.03 without (gate_up 318 vs 322 us), stage-1 step 216.0 ms WITH it against 213.5 without --
-// hardware dispatch already starts the next workgroup's prologue while other CUs store, and it balances the ragged last
-// m-tile rows of the training shapes dynamically, which a static walk cannot.  Kept as a switch for later A/B runs.
-bool persist_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VGPT_GEMM_PERSIST");
-        v = e ? (atoi(e) != 0) : 0;
-    }
-    return v != 0;
-}
-
 int cu_count() {
     static int v = 0;
     if (v == 0) {
@@ -1460,11 +1283,11 @@ void launch_recs_add(int kernel, int mode, bool atr, bool wtr, int rows) {
     ++g_n_launch_recs;
 }
 
-template <int MODE, typename C, int PIPE, bool ATR = false, bool WTR = false>
+template <int MODE, typename C, bool ATR = false, bool WTR = false>
 int launch_cfg(GemmArgs g, int64_t n_out, hipStream_t s, const char* name) {
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<MODE, C, PIPE, ATR, WTR>,
+        hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<MODE, C, ATR, WTR>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES + C::BM * 4);
         if (e != hipSuccess) {
             vgpt_set_error("%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
@@ -1474,46 +1297,25 @@ int launch_cfg(GemmArgs g, int64_t n_out, hipStream_t s, const char* name) {
     }
     g.tiles_m = (int)cdiv(g.M, C::BM);
     g.tiles_n = (int)cdiv(n_out, MODE == MODE_GATED ? C::BN / 2 : C::BN);
-    // persistent walk (kernel: PERSIST): one round of the chip's workgroup slots, each workgroup taking tiles
-    // blockIdx.x, + gridDim.x, ...; the slot count is a multiple of 8 (XCD remap).  Off by default (persist_enabled()).
-    int grid = g.tiles_m * g.tiles_n;
-    if ((PIPE == 0 || PIPE == 1) && MODE != MODE_ROPE && persist_enabled() && g.nrm_rstd == nullptr) {
-        const int slots = cu_count() * (C::LDS_BYTES > 80 * 1024 ? 1 : 2);
-        if (slots % 8 == 0 && grid > slots) grid = slots;
-    }
-    hipLaunchKernelGGL((gemm_bf16_kernel<MODE, C, PIPE, ATR, WTR>), dim3(grid), dim3(C::THREADS),
+    hipLaunchKernelGGL((gemm_bf16_kernel<MODE, C, ATR, WTR>), dim3(g.tiles_m * g.tiles_n), dim3(C::THREADS),
                        C::LDS_BYTES + C::BM * 4, s, g);
     VGPT_CHECK_LAUNCH(name);
     launch_recs_add(C::BM == 128 ? 128 : C::BN, MODE, ATR, WTR, g.M);
     return VGPT_OK;
 }
 
-// 0 = heuristic, 128 / 256 / 192 / 288 = forced tile, 257 / 289 = the 256- / 288-wide tile with the simple (non-pipelined) loop
-// (VGPT_GEMM_TILE, read once; for A/B measurements)
-int forced_tile() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VGPT_GEMM_TILE");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
-
-// Launch plan of a big-tile GEMM: the big-tile kernel (one block per CU, so T tiles take ceil(T/256) rounds) gets either
-// everything or — when the last round would be badly filled — only the m-tile rows that make full rounds, and the
+// Launch plan of an eight-wave big-tile GEMM: the big-tile kernel (one block per CU, so T tiles take ceil(T/256) rounds) gets
+// either everything or — when the last round would be badly filled — only the m-tile rows that make full rounds, and the
 // 128x128 kernel (2 blocks/CU, 4x smaller tiles) runs the remaining rows behind it.
-// Costs are in units of one 256-row big-tile ROUND.  A round takes the same time whatever the tile's width (1.57 us per
-// k-tile with 256 x 192 tiles against 1.62 with 256 x 256: the loop waits on its operand stream, not on the MFMAs), so a
-// narrower tile only pays where it removes a badly filled round; a round of the 128-tile kernel (512 tiles) measured at
-// 0.62 of a big round (46 us against 75-78 at K = 3072).
+// The cost is in units of one k-tile of a round of 256x256 tiles: a round of 256x256 tiles costs 1.0 per k-tile, a round of
+// 256x192 tiles 0.77, every round 7.0 more for its prologue and epilogue (nothing overlaps them with one workgroup per CU),
+// and a round of the 128x128 kernel (512 tiles) 0.62 of a 256x256 round; a split plan is taken when the last round would be
+// under 85 % full and the split costs under 0.97 of the whole.  (Fitted at M = 4096 over K = 1024 .. 8192,
+// scripts/gemm_k_sweep.py.)
 struct BigPlan {
     int64_t rows_big;  // rows given to the big-tile kernel (M: no split)
     double cost;
 };
-// Cost of a launch plan in units of one k-tile of a 256x256 workgroup tile.  Measured at M = 4096 over K = 1024 .. 8192
-// (scripts/gemm_k_sweep.py): a round of 256x256 tiles takes 1.0 per k-tile, a round of 256x192 tiles 0.77 (its 48 instead
-// of 64 MFMAs per wave), and every round pays about 7 more for its prologue and epilogue (nothing overlaps them with one
-// workgroup per CU); a round of the 128x128 kernel (two workgroups per CU) runs 0.62 of a 256x256 round.
 BigPlan plan_big(int64_t M, int64_t n_out, int bn_out, int64_t nk) {
     constexpr int CUS = 256;
     constexpr double FIXED = 7.0;
@@ -1534,10 +1336,9 @@ BigPlan plan_big(int64_t M, int64_t n_out, int bn_out, int64_t nk) {
     return {M, whole};
 }
 
-// Which kernel family big NT products take: 0 = the four-wave kernel wherever w4_ok() (default), 1 = the eight-wave LDS-DMA
+// Which kernel family big products take: 0 = the four-wave kernel wherever w4_ok() (default), 1 = the eight-wave LDS-DMA
 // kernels only (parity tests run both; same-box A/B).  Set through vgpt_gemm_set_family.
 int g_family = 0;
-bool w4_enabled() { return g_family == 0; }
 
 template <int MODE, int NI, bool WTR = false, bool ATR = false>
 int launch_w4_cfg(GemmArgs g, int64_t n_out, hipStream_t s, const char* name) {
@@ -1563,15 +1364,19 @@ int launch_w4_cfg(GemmArgs g, int64_t n_out, hipStream_t s, const char* name) {
     return VGPT_OK;
 }
 
-// Shapes the four-wave kernel takes: NT operands, at least two k-tiles, 8 rows / columns to clamp into, every byte offset the
-// loop forms below 2 GiB (A: relative to the tile's first row; W: relative to the matrix for the row-permuting modes)
-template <int MODE>
+// Strides and shapes the four-wave kernel takes: at least two k-tiles, 8 rows / columns to clamp into, every byte offset the loop
+// forms below 2 GiB.  NT operands: whole k-tiles; A relative to the tile's first row, W relative to the matrix (the
+// row-permuting modes).  A transposed operand (dX: W, dW: both) is addressed by reduction row, one k-tile past K; only dW takes
+// a partial last k-tile (zero-filled by its descriptors).
+template <int MODE, bool ATR, bool WTR>
 bool w4_ok(const GemmArgs& g, int64_t n_out) {
-    const int64_t rows_w = MODE == MODE_GATED ? 2 * (int64_t)g.I : g.N;
-    if (g.K % BK != 0 || g.K < 2 * BK || g.M < 8 || n_out < 8 || rows_w < 8) return false;
-    if (MODE == MODE_GATED && g.I < 8) return false;
-    if ((256 + 8) * g.lda * 2 + (int64_t)g.K * 2 >= (1ll << 31)) return false;
-    if ((rows_w + 8) * g.ldw * 2 + (int64_t)g.K * 2 >= (1ll << 31)) return false;
+    static_assert(!ATR || WTR, "a transposed A comes with a transposed W");
+    static_assert(!WTR || MODE == MODE_PLAIN, "transposed operands: plain kernel only");
+    const int64_t rows_w = MODE == MODE_GATED ? 2 * (int64_t)g.I : g.N, lim = 1ll << 31;
+    if (g.K < 2 * BK || g.M < 8 || n_out < 8 || rows_w < 8) return false;
+    if (!ATR && g.K % BK != 0) return false;
+    if (ATR ? ((int64_t)g.K + 64) * g.lda * 2 >= lim : (256 + 8) * g.lda * 2 + (int64_t)g.K * 2 >= lim) return false;
+    if (WTR ? ((int64_t)g.K + 64) * g.ldw * 2 >= lim : (rows_w + 8) * g.ldw * 2 + (int64_t)g.K * 2 >= lim) return false;
     if (g.ldc >= (1 << 21) || g.ldr >= (1 << 21) || g.ld_gu >= (1 << 21)) return false;   // 256 rows x ld x 2 bytes below the descriptors' range
     if (MODE == MODE_ROPE) {   // the epilogue stages the tile's cos / sin rows through LDS (two tables of 256 x head_dim / 2 floats)
         const int tab_bytes = (256 * (g.head_dim >> 1) * 4 + 1023) & ~1023;
@@ -1593,13 +1398,6 @@ void w4_costs(const GemmArgs& g, int64_t n_out, double& c256, double& c192) {
     c256 = (double)cdiv(t256, cus) * ((double)nk + FIXED);
     c192 = (double)cdiv(t192, cus) * (0.89 * (double)nk + FIXED);
 }
-// the cheaper of the two in units of one 256-wide round
-template <int MODE>
-double w4_cost_rounds(const GemmArgs& g, int64_t n_out) {
-    double c256, c192;
-    w4_costs<MODE>(g, n_out, c256, c192);
-    return (c192 < c256 ? c192 : c256) / ((double)(g.K / BK) + 13.5);
-}
 
 // 256 x 288 tiles (NI = 9: whole tiles only, no gated mode): a k-tile is 144 instead of 128 MFMAs per wave
 template <int MODE>
@@ -1619,100 +1417,68 @@ int w4_forced_ni() {
     return forced;
 }
 
-// 192- rather than 256-wide tiles for a product of these costs: the ONE decision behind both the launch and the partial-sum
-// count of the folded RMSNorm's workspace (norm_partials), so a forced width cannot make them disagree
-bool w4_use192(double c256, double c192) {
-    const int forced = w4_forced_ni();
-    return forced == 6 || (forced != 8 && c192 < c256);
-}
-
-template <int MODE>
-int launch_w4(const GemmArgs& g, int64_t n_out, hipStream_t s, const char* name) {
+// THE launch decision of the four-wave kernel: its NI (8 / 6 / 9 = 256- / 192- / 288-wide tiles) for this product, or 0 where
+// the eight-wave kernels take it (family 1, a grid under half the chip, a shape or stride outside w4_ok).  Behind the launch
+// and, with `partials`, behind the partial-sum count of the folded RMSNorm's workspace, so the two cannot disagree.
+// partials: the product leaves per-row partial sums of squares (vgpt_gemm_bf16_resid_rstd), which 288-wide tiles do not.
+// The transposed forms take the cost model's width whatever VGPT_GEMM_W4_NI says, and have no 288-wide loop.
+template <int MODE, bool ATR, bool WTR>
+int w4_ni(const GemmArgs& g, int64_t n_out, bool partials) {
+    const int64_t big_tiles = cdiv(g.M, 256) * cdiv(n_out, MODE == MODE_GATED ? 128 : 256);
+    if (g_family != 0 || big_tiles < 128 || !w4_ok<MODE, ATR, WTR>(g, n_out)) return 0;
     double c256, c192;
     w4_costs<MODE>(g, n_out, c256, c192);
-    const double c288 = w4_cost288<MODE>(g, n_out);
+    if (ATR || WTR) return c192 < c256 ? 6 : 8;
     const int forced = w4_forced_ni();
-    if constexpr (MODE != MODE_GATED) {
-        if (c288 < 1e29 && g.ssq_out == nullptr && (forced == 9 || (forced == 0 && c288 < c256 && c288 < c192)))
-            return launch_w4_cfg<MODE, 9>(g, n_out, s, name);
+    const double c288 = w4_cost288<MODE>(g, n_out);
+    if (c288 < 1e29 && !partials && (forced == 9 || (forced == 0 && c288 < c256 && c288 < c192))) return 9;
+    return forced == 6 || (forced != 8 && c192 < c256) ? 6 : 8;
+}
+
+template <int MODE, bool ATR, bool WTR>
+int launch_w4(int ni, const GemmArgs& g, int64_t n_out, hipStream_t s, const char* name) {
+    if constexpr (MODE != MODE_GATED && !WTR) {
+        if (ni == 9) return launch_w4_cfg<MODE, 9>(g, n_out, s, name);
     }
-    if (w4_use192(c256, c192)) return launch_w4_cfg<MODE, 6>(g, n_out, s, name);
-    return launch_w4_cfg<MODE, 8>(g, n_out, s, name);
+    if (ni == 6) return launch_w4_cfg<MODE, 6, WTR, ATR>(g, n_out, s, name);
+    return launch_w4_cfg<MODE, 8, WTR, ATR>(g, n_out, s, name);
 }
 
 template <int MODE, bool ATR = false, bool WTR = false>
 int launch(const GemmArgs& g, int64_t n_out, hipStream_t s, const char* name) {
-    const int f = forced_tile();
-    // the 256-tile pays off once the grid fills the chip (>= ~half of the 256 CUs with 256x256 tiles)
-    const int64_t tiles_n = cdiv(n_out, MODE == MODE_GATED ? 128 : 256);
+    constexpr bool NT = !ATR && !WTR;
+    // the 256-row tiles pay off once the grid fills the chip (>= ~half of the 256 CUs with 256x256 tiles)
     const int64_t tiles_m = cdiv(g.M, 256);
-    const int64_t big_tiles = tiles_m * tiles_n;
-    const bool use256 = f == 256 || f == 257 || f == 192 || f == 288 || f == 289 || f == 512 || (f != 128 && big_tiles >= 128);
-    if (!use256) return launch_cfg<MODE, Cfg128, 0, ATR, WTR>(g, n_out, s, name);
-    if constexpr (!ATR && !WTR) {
-        if (f == 0 && w4_enabled() && w4_ok<MODE>(g, n_out)) {
-            return launch_w4<MODE>(g, n_out, s, name);
-        }
-    }
-    if constexpr (!ATR && WTR && MODE == MODE_PLAIN) {
-        // dX = dY W of the backward on the four-wave kernel (fragments of W by ds_read_b64_tr_b16): one launch for all rows --
-        // the eight-wave plan splits a 7740-row product at a round boundary and re-streams W for the remainder
-        if (f == 0 && w4_enabled() && g.K % BK == 0 && g.K >= 2 * BK && g.M >= 8 && n_out >= 8 &&
-            (256 + 8) * g.lda * 2 + (int64_t)g.K * 2 < (1ll << 31) && ((int64_t)g.K + 64) * g.ldw * 2 < (1ll << 31) &&
-            g.ldc < (1 << 21) && g.ldr < (1 << 21)) {
-            double c256, c192;
-            w4_costs<MODE>(g, n_out, c256, c192);
-            if (c192 < c256) return launch_w4_cfg<MODE, 6, true>(g, n_out, s, name);
-            return launch_w4_cfg<MODE, 8, true>(g, n_out, s, name);
-        }
-    }
-    if constexpr (ATR && WTR && MODE == MODE_PLAIN) {
-        // dW = dY^T X of the backward on the four-wave kernel: both images natural [64 reduction rows][256 columns], fragments
-        // of both operands by ds_read_b64_tr_b16
-        if (f == 0 && w4_enabled() && g.K >= 2 * BK && g.M >= 8 && n_out >= 8 && big_tiles >= 128 &&
-            ((int64_t)g.K + 64) * g.lda * 2 < (1ll << 31) && ((int64_t)g.K + 64) * g.ldw * 2 < (1ll << 31) &&
-            g.ldc < (1 << 21) && g.ldr < (1 << 21)) {
-            double c256, c192;
-            w4_costs<MODE>(g, n_out, c256, c192);
-            if (c192 < c256) return launch_w4_cfg<MODE, 6, true, true>(g, n_out, s, name);
-            return launch_w4_cfg<MODE, 8, true, true>(g, n_out, s, name);
-        }
-    }
-    if (f == 257) return launch_cfg<MODE, Cfg256, 0, ATR, WTR>(g, n_out, s, name);
-    if constexpr ((MODE == MODE_PLAIN || MODE == MODE_ROPE) && !ATR && !WTR) {
-        if (f == 288) return launch_cfg<MODE, Cfg288, 5, ATR, WTR>(g, n_out, s, name);
-        if (f == 289) return launch_cfg<MODE, Cfg288, 0, ATR, WTR>(g, n_out, s, name);
-    }
+    if (tiles_m * cdiv(n_out, MODE == MODE_GATED ? 128 : 256) < 128) return launch_cfg<MODE, Cfg128, ATR, WTR>(g, n_out, s, name);
+    // the four-wave kernel, one launch for all rows (the eight-wave plan below splits a 7740-row product at a round boundary
+    // and re-streams W for the remainder)
+    if (const int ni = w4_ni<MODE, ATR, WTR>(g, n_out, g.ssq_out != nullptr)) return launch_w4<MODE, ATR, WTR>(ni, g, n_out, s, name);
+    // eight-wave kernels: 256 x 256 tiles, or (NT plain / RoPE) 256 x 192 tiles when their rounds fit the problem better
     const int64_t nk = cdiv(g.K, BK);
-    BigPlan p256 = plan_big(g.M, n_out, MODE == MODE_GATED ? 128 : 256, nk);
-    if (f == 256) p256.rows_big = g.M;
+    BigPlan p = plan_big(g.M, n_out, MODE == MODE_GATED ? 128 : 256, nk);
     bool use192 = false;
-    BigPlan p = p256;
-    if constexpr ((MODE == MODE_PLAIN || MODE == MODE_ROPE) && !ATR && !WTR) {
-        // 256 x 192 tiles when their rounds fit the problem better
-        BigPlan p192 = plan_big(g.M, n_out, 192, nk);
-        if (f == 192) p192.rows_big = g.M;
-        use192 = f == 192 || (f == 0 && p192.cost < 0.985 * p256.cost);
+    if constexpr (NT && MODE != MODE_GATED) {
+        const BigPlan p192 = plan_big(g.M, n_out, 192, nk);
+        use192 = p192.cost < 0.985 * p.cost;
         if (use192) p = p192;
-    }
-    // 256 x 288 tiles (a round costs ~1.3 of a 256 x 256 round at the same K -- 72 instead of 64 MFMAs per wave and k-tile;
-    // 1.35 is the simple loop's figure, VGPT_GEMM_TILE=289) where they divide N and save enough rounds -- in practice
-    // qkv_proj (N = 9216) of a 4096-row sampler step: two rounds against three of 192-wide tiles, 203 vs 225-230 us with
-    // weights from HBM (scripts/gemm_epilogue_probe.py, same box)
-    if constexpr ((MODE == MODE_PLAIN || MODE == MODE_ROPE) && !ATR && !WTR) {
-        if (f == 0 && n_out % 288 == 0 && p.rows_big >= g.M) {
+        // 256 x 288 tiles (a round costs 1.35 of a 256 x 256 round at the same K: 72 instead of 64 MFMAs per wave and k-tile)
+        // where they divide N and save enough rounds of an unsplit plan -- in practice qkv_proj (N = 9216) of a 4096-row
+        // sampler step: two rounds against three of 192-wide tiles, 203 vs 225-230 us with weights from HBM
+        // (scripts/gemm_epilogue_probe.py, same box)
+        if (n_out % 288 == 0 && p.rows_big >= g.M) {
             const double r288 = (double)cdiv(tiles_m * (n_out / 288), 256) * 1.35;
             const double rcur = (double)cdiv(tiles_m * cdiv(n_out, use192 ? 192 : 256), 256);
-            if (r288 < 0.95 * rcur) return launch_cfg<MODE, Cfg288, 5, ATR, WTR>(g, n_out, s, name);
+            if (r288 < 0.95 * rcur) return launch_cfg<MODE, Cfg288, ATR, WTR>(g, n_out, s, name);
         }
     }
     auto big = [&](const GemmArgs& ga) {
-        if constexpr ((MODE == MODE_PLAIN || MODE == MODE_ROPE) && !ATR && !WTR) {
-            if (use192) return launch_cfg<MODE, Cfg192, 1, ATR, WTR>(ga, n_out, s, name);
+        if constexpr (NT && MODE != MODE_GATED) {
+            if (use192) return launch_cfg<MODE, Cfg192, ATR, WTR>(ga, n_out, s, name);
         }
-        return launch_cfg<MODE, Cfg256, 1, ATR, WTR>(ga, n_out, s, name);
+        return launch_cfg<MODE, Cfg256, ATR, WTR>(ga, n_out, s, name);
     };
     if (p.rows_big >= g.M) return big(g);
+    // split plan: the rows that make full rounds on the big tiles, the rest on the 128 x 128 kernel through offset pointers
     GemmArgs g1 = g, g2 = g;
     const int64_t m1 = p.rows_big;
     g1.M = (int)m1;
@@ -1729,7 +1495,7 @@ int launch(const GemmArgs& g, int64_t n_out, hipStream_t s, const char* name) {
     int rc = big(g1);
     if (rc != VGPT_OK) return rc;
     g_launch_row0 = (int)m1;
-    return launch_cfg<MODE, Cfg128, 0, ATR, WTR>(g2, n_out, s, name);
+    return launch_cfg<MODE, Cfg128, ATR, WTR>(g2, n_out, s, name);
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -1763,16 +1529,15 @@ VGPT_EXPORT int vgpt_gemm_last_launches(int32_t* out, int cap) {
 
 /* ---- RMSNorm folded into the GEMMs around it ---- */
 namespace {
-// partial sums per row for this shape on the four-wave kernel; 0: not a shape it takes
+// partial sums per row for this shape on the four-wave kernel (two per tile column: one per wave column); 0: not a shape it
+// takes.  Decided on dense strides by the launch's own w4_ni.
 int norm_partials(int64_t M, int64_t N, int64_t K) {
     if (M <= 0 || N <= 0 || K <= 0 || M >= (1 << 30) || N >= (1 << 30) || K >= (1 << 30)) return 0;
     GemmArgs g;
     g.M = (int)M; g.N = (int)N; g.K = (int)K;
     g.lda = K; g.ldw = K; g.ldc = N; g.ldr = N; g.I = 0;
-    if (g_family != 0 || forced_tile() != 0 || cdiv(M, 256) * cdiv(N, 256) < 128 || !w4_ok<MODE_PLAIN>(g, N)) return 0;
-    double c256, c192;
-    w4_costs<MODE_PLAIN>(g, N, c256, c192);
-    return 2 * (int)cdiv(N, w4_use192(c256, c192) ? 192 : 256);
+    const int ni = w4_ni<MODE_PLAIN, false, false>(g, N, true);
+    return ni == 0 ? 0 : 2 * (int)cdiv(N, ni * 32);
 }
 int64_t norm_cnt_bytes(int64_t M) { return (cdiv(M, 256) * 4 + 255) / 256 * 256; }
 }  // namespace
@@ -1808,11 +1573,12 @@ VGPT_EXPORT int vgpt_gemm_bf16_resid_rstd(const void* A, const void* W, void* C,
     g.ssq_cnt = (int*)workspace;
     g.ssq_out = (float*)((char*)workspace + norm_cnt_bytes(M));
     g.rstd_out = rstd_out; g.nrm_ld = M; g.nrm_eps = eps; g.nrm_inv_h = 1.0f / (float)N;
-    // the workspace size was decided on dense strides; the launch uses the caller's
-    VGPT_REQUIRE(w4_ok<MODE_PLAIN>(g, N), VGPT_ERR_UNSUPPORTED,
+    // the workspace size was decided on dense strides; the launch uses the caller's (the tile width depends on neither)
+    const int ni = w4_ni<MODE_PLAIN, false, false>(g, N, true);
+    VGPT_REQUIRE(ni != 0, VGPT_ERR_UNSUPPORTED,
                  "vgpt_gemm_bf16_resid_rstd: row strides beyond the four-wave kernel's offset range (ldc, ldr < 2^21; 264 rows of A "
                  "and N + 8 rows of W below 2 GiB)");
-    return launch_w4<MODE_PLAIN>(g, N, (hipStream_t)stream, "vgpt_gemm_bf16_resid_rstd");
+    return launch_w4<MODE_PLAIN, false, false>(ni, g, N, (hipStream_t)stream, "vgpt_gemm_bf16_resid_rstd");
 }
 
 VGPT_EXPORT int vgpt_gemm_bf16(const void* A, const void* W, void* C, const void* extra, int64_t M,
