@@ -532,6 +532,26 @@ int vgpt_clip_coef(const float* sumsq, int n, float* coef, float* norm_out, floa
 int vgpt_adamw_step(float* master, void* param, const void* grad, int grad_f32, float* m, float* v, int64_t n, float lr,
                     float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale,
                     void* stream);
+/* EMA of the weights (train_x1_stage1_noiseinput.py:227-230, 288-290, 406-408; update_ema, LVM/utils.py:27-34) inside the
+ * AdamW pass: vgpt_adamw_step with a fourth fp32 stream.  master, param, m and v are updated by the same expressions in the
+ * same order (bit-identical to vgpt_adamw_step on the same inputs), and ema[i] = fmaf(d, ema[i], (1 - d) * p_new[i]) with
+ * d = ema_decay, 1 - d formed in fp32 on the host and p_new the fp32 master value just computed (not its bf16 rounding):
+ * the product (1 - d) * p_new is rounded to fp32, then ONE fused multiply-add, two roundings in all.  d = 0 gives
+ * ema = p_new bit for bit, d = 1 leaves a finite ema unchanged (a -0 becomes +0).  36 B/param in one pass (a separate EMA
+ * pass behind vgpt_adamw_step: 28 + 12).  Same alignment contract, ema held to the 16-byte rule (VGPT_ERR_UNSUPPORTED);
+ * a NULL ema, n < 0, step < 1 or ema_decay outside [0, 1]: VGPT_ERR_INVALID; n == 0: VGPT_OK. */
+int vgpt_adamw_ema_step(float* master, void* param, const void* grad, int grad_f32, float* m, float* v, int64_t n, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale,
+                        float* ema, float ema_decay, void* stream);
+/* Gradient accumulation over micro-steps (--gradient_accumulation_steps, train_x1_stage1_noiseinput.py:121, 353
+ * accelerator.accumulate, 393, 406-413): acc is an fp32 accumulator of n elements, grad the gradient bucket (bf16, or fp32
+ * when grad_f32 != 0).  mode 0: acc = float(grad) (first micro-step); mode 1: acc += float(grad) (middle micro-steps);
+ * mode 2: grad = T(acc + float(grad)) written back in the bucket's own type (bf16: round to nearest even), acc NOT written
+ * (last micro-step): the bucket then holds the once-rounded sum of all micro-gradients and the exchange, vgpt_sumsq,
+ * vgpt_clip_coef and vgpt_adamw_step run on it unchanged.  Elementwise: deterministic.  acc and an fp32 grad 16-byte
+ * aligned, a bf16 grad 8-byte aligned (else VGPT_ERR_UNSUPPORTED); a NULL pointer, n < 0 or another mode:
+ * VGPT_ERR_INVALID; n == 0: VGPT_OK. */
+int vgpt_grad_accumulate(float* acc, void* grad, int grad_f32, int64_t n, int mode, void* stream);
 
 /* ---- LoRA adapters (LVM/train/train_x1_stage1_noiseinput.py:204-223, peft LoraConfig on qkv_proj / o_proj; the merge of
  *      LVM/pipeline.py:97-101) ------------------------------------------------------------------------------------------

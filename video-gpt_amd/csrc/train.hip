@@ -535,12 +535,15 @@ __global__ __launch_bounds__(64) void sumsq_final_kernel(const float* __restrict
 // AdamW (torch.optim.AdamW semantics) on fp32 master weights; bf16 model copy refreshed.
 // grad_scale_ptr: device scalar multiplied into the gradient (clip coefficient / 1/world), may be NULL.
 // Four elements per thread: 16-byte accesses on the three fp32 streams (28 B/param of traffic, HBM-bound).
-template <typename TG>
+// EMA (vgpt_adamw_ema_step): a fourth fp32 stream in the same pass, ema = fmaf(d, ema, (1 - d) * p_new) on the fp32 master
+// value just computed (36 B/param); a template parameter, so the plain instantiation carries none of it.
+template <typename TG, bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, bf16* __restrict__ param,
                                                     const TG* __restrict__ grad, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, float lr, float b1, float b2,
                                                     float eps, float wd, float bc1, float bc2,
-                                                    const float* __restrict__ grad_scale_ptr) {
+                                                    const float* __restrict__ grad_scale_ptr, float* __restrict__ ema,
+                                                    float ema_d, float ema_omd) {
     const float gs = grad_scale_ptr ? *grad_scale_ptr : 1.0f;
     // torch.optim.AdamW: p -= lr (m/bc1) / (sqrt(v/bc2) + eps).  The two bias corrections are folded into constants
     // and the one remaining division is v_rcp_f32 (1 ulp) on a term that is ~lr relative to p.
@@ -557,6 +560,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, 
         f32x4 p4 = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(master) + i);
         f32x4 m4 = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(m) + i);
         f32x4 v4 = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(v) + i);
+        f32x4 e4;
+        if constexpr (EMA) e4 = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(ema) + i);
         float g4[4];
         if constexpr (sizeof(TG) == 2) {
             const bf16x4 gb = reinterpret_cast<const bf16x4*>(grad)[i];
@@ -574,11 +579,13 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, 
             upd(g4[t], p, mi, vi);
             p4[t] = p; m4[t] = mi; v4[t] = vi;
             o[t] = f2bf(p);
+            if constexpr (EMA) e4[t] = fmaf(ema_d, e4[t], ema_omd * p);
         }
         // streamed once per step: keep them out of the caches
         __builtin_nontemporal_store(p4, reinterpret_cast<f32x4*>(master) + i);
         __builtin_nontemporal_store(m4, reinterpret_cast<f32x4*>(m) + i);
         __builtin_nontemporal_store(v4, reinterpret_cast<f32x4*>(v) + i);
+        if constexpr (EMA) __builtin_nontemporal_store(e4, reinterpret_cast<f32x4*>(ema) + i);
         reinterpret_cast<bf16x4*>(param)[i] = o;
     }
     for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {  // tail (< 4)
@@ -586,6 +593,45 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, 
         upd((float)grad[i], p, mi, vi);
         master[i] = p; m[i] = mi; v[i] = vi;
         param[i] = f2bf(p);
+        if constexpr (EMA) ema[i] = fmaf(ema_d, ema[i], ema_omd * p);
+    }
+}
+
+// Gradient accumulation over micro-steps (train_x1_stage1_noiseinput.py:353, accelerator.accumulate): fp32 accumulator, the
+// gradient bucket in its own type.  MODE 0: acc = float(g); 1: acc += float(g); 2: g = TG(acc + float(g)), acc not written.
+// Elementwise (deterministic), one 4-element vector per thread like adamw_kernel; the accumulator is streamed once per
+// micro-step (non-temporal), the bucket written by mode 2 is read next by the exchange / sumsq (plain store).
+template <typename TG, int MODE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, TG* __restrict__ grad, int64_t n) {
+    const int64_t n4 = n >> 2, i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n4) {
+        f32x4 g4;
+        if constexpr (sizeof(TG) == 2) {
+            const bf16x4 gb = reinterpret_cast<const bf16x4*>(grad)[i];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) g4[t] = bf2f(gb[t]);
+        } else {
+            g4 = reinterpret_cast<const f32x4*>(grad)[i];
+        }
+        if constexpr (MODE != 0) g4 += __builtin_nontemporal_load(reinterpret_cast<f32x4*>(acc) + i);
+        if constexpr (MODE != 2) {
+            __builtin_nontemporal_store(g4, reinterpret_cast<f32x4*>(acc) + i);
+        } else if constexpr (sizeof(TG) == 2) {
+            bf16x4 o;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) o[t] = f2bf(g4[t]);
+            reinterpret_cast<bf16x4*>(grad)[i] = o;
+        } else {
+            reinterpret_cast<f32x4*>(grad)[i] = g4;
+        }
+    }
+    const int64_t j = (n4 << 2) + i;      // tail (< 4): the first threads of the grid
+    if (j < n) {
+        float s = (float)grad[j];
+        if constexpr (MODE != 0) s += acc[j];
+        if constexpr (MODE != 2) acc[j] = s;
+        else if constexpr (sizeof(TG) == 2) grad[j] = f2bf(s);
+        else grad[j] = s;
     }
 }
 
@@ -884,26 +930,70 @@ VGPT_EXPORT int vgpt_clip_coef(const float* sumsq, int n, float* coef, float* no
     LAUNCH_OK("vgpt_clip_coef");
 }
 
+// shared by vgpt_adamw_step (ema == NULL) and vgpt_adamw_ema_step
+static int adamw_launch(const char* name, float* master, void* param, const void* grad, int grad_f32, float* m, float* v,
+                        int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                        const float* grad_scale, float* ema, float ema_decay, void* stream) {
+    // in double, as torch.optim.AdamW does: 1 - beta2^step cancels at small steps (1 - powf(0.999f, 2) in fp32 is 6.7e-6
+    // off, relative), and that error went straight into every update of the first steps
+    const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step)),
+                bc2 = (float)(1.0 - std::pow((double)beta2, (double)step));
+    VGPT_REQUIRE(((((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0) &&
+                     (((uintptr_t)param | (uintptr_t)grad) & 7) == 0 && (!grad_f32 || ((uintptr_t)grad & 15) == 0),
+                 VGPT_ERR_UNSUPPORTED, "%s: buffers must be 16-byte (fp32) / 8-byte (bf16) aligned", name);
+    // one 4-element vector per thread: measured 6.45 TB/s against 5.6 TB/s for a 4096-workgroup grid-stride loop
+    int grid = (int)std::min<int64_t>(cdiv(cdiv(n, 4), 256), (int64_t)1 << 30);
+    const float omd = 1.0f - ema_decay;
+#define VGPT_ADAMW_LAUNCH(TG, EMA)                                                                                        \
+    hipLaunchKernelGGL((adamw_kernel<TG, EMA>), dim3(grid), dim3(256), 0, (hipStream_t)stream, master, (bf16*)param,      \
+                       (const TG*)grad, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, ema, ema_decay, \
+                       omd)
+    if (ema) { if (grad_f32) VGPT_ADAMW_LAUNCH(float, true); else VGPT_ADAMW_LAUNCH(bf16, true); }
+    else     { if (grad_f32) VGPT_ADAMW_LAUNCH(float, false); else VGPT_ADAMW_LAUNCH(bf16, false); }
+#undef VGPT_ADAMW_LAUNCH
+    VGPT_CHECK_LAUNCH(name);
+    return VGPT_OK;
+}
+
 VGPT_EXPORT int vgpt_adamw_step(float* master, void* param, const void* grad, int grad_f32, float* m, float* v,
                                 int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                 const float* grad_scale, void* stream) {
     VGPT_REQUIRE(master && param && grad && m && v, VGPT_ERR_INVALID, "vgpt_adamw_step: null pointer");
     VGPT_REQUIRE(n >= 0 && step >= 1, VGPT_ERR_INVALID, "vgpt_adamw_step: bad argument");
     if (n == 0) return VGPT_OK;
-    // in double, as torch.optim.AdamW does: 1 - beta2^step cancels at small steps (1 - powf(0.999f, 2) in fp32 is 6.7e-6
-    // off, relative), and that error went straight into every update of the first steps
-    const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step)),
-                bc2 = (float)(1.0 - std::pow((double)beta2, (double)step));
-    VGPT_REQUIRE(((((uintptr_t)master | (uintptr_t)m | (uintptr_t)v) & 15) == 0) && (((uintptr_t)param | (uintptr_t)grad) & 7) == 0 &&
-                     (!grad_f32 || ((uintptr_t)grad & 15) == 0),
-                 VGPT_ERR_UNSUPPORTED, "vgpt_adamw_step: buffers must be 16-byte (fp32) / 8-byte (bf16) aligned");
-    // one 4-element vector per thread: measured 6.45 TB/s against 5.6 TB/s for a 4096-workgroup grid-stride loop
-    int grid = (int)std::min<int64_t>(cdiv(cdiv(n, 4), 256), (int64_t)1 << 30);
-    if (grad_f32)
-        hipLaunchKernelGGL(adamw_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, master, (bf16*)param,
-                           (const float*)grad, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale);
-    else
-        hipLaunchKernelGGL(adamw_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, master, (bf16*)param,
-                           (const bf16*)grad, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale);
-    LAUNCH_OK("vgpt_adamw_step");
+    return adamw_launch("vgpt_adamw_step", master, param, grad, grad_f32, m, v, n, lr, beta1, beta2, eps, weight_decay, step,
+                        grad_scale, nullptr, 0.f, stream);
+}
+
+VGPT_EXPORT int vgpt_adamw_ema_step(float* master, void* param, const void* grad, int grad_f32, float* m, float* v,
+                                    int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                    const float* grad_scale, float* ema, float ema_decay, void* stream) {
+    VGPT_REQUIRE(master && param && grad && m && v && ema, VGPT_ERR_INVALID, "vgpt_adamw_ema_step: null pointer");
+    VGPT_REQUIRE(n >= 0 && step >= 1 && ema_decay >= 0.f && ema_decay <= 1.f, VGPT_ERR_INVALID,
+                 "vgpt_adamw_ema_step: bad argument");
+    if (n == 0) return VGPT_OK;
+    return adamw_launch("vgpt_adamw_ema_step", master, param, grad, grad_f32, m, v, n, lr, beta1, beta2, eps, weight_decay,
+                        step, grad_scale, ema, ema_decay, stream);
+}
+
+VGPT_EXPORT int vgpt_grad_accumulate(float* acc, void* grad, int grad_f32, int64_t n, int mode, void* stream) {
+    VGPT_REQUIRE(acc && grad, VGPT_ERR_INVALID, "vgpt_grad_accumulate: null pointer");
+    VGPT_REQUIRE(n >= 0 && mode >= 0 && mode <= 2, VGPT_ERR_INVALID, "vgpt_grad_accumulate: bad argument (n %lld, mode %d)",
+                 (long long)n, mode);
+    if (n == 0) return VGPT_OK;
+    VGPT_REQUIRE(((uintptr_t)acc & 15) == 0 && ((uintptr_t)grad & (grad_f32 ? 15 : 7)) == 0, VGPT_ERR_UNSUPPORTED,
+                 "vgpt_grad_accumulate: buffers must be 16-byte (fp32) / 8-byte (bf16) aligned");
+    // one 4-element vector per thread, as vgpt_adamw_step; cdiv(n, 4) threads also cover the tail of n % 4 elements
+    const int64_t blocks = cdiv(cdiv(n, 4), 256);
+    VGPT_REQUIRE(blocks <= ((int64_t)1 << 31) - 1, VGPT_ERR_UNSUPPORTED, "vgpt_grad_accumulate: n too large");
+    const dim3 grid((unsigned)blocks);
+#define VGPT_ACC_LAUNCH(TG, MODE)                                                                                     \
+    hipLaunchKernelGGL((grad_accumulate_kernel<TG, MODE>), grid, dim3(256), 0, (hipStream_t)stream, acc, (TG*)grad, n)
+    if (grad_f32) {
+        if (mode == 0) VGPT_ACC_LAUNCH(float, 0); else if (mode == 1) VGPT_ACC_LAUNCH(float, 1); else VGPT_ACC_LAUNCH(float, 2);
+    } else {
+        if (mode == 0) VGPT_ACC_LAUNCH(bf16, 0); else if (mode == 1) VGPT_ACC_LAUNCH(bf16, 1); else VGPT_ACC_LAUNCH(bf16, 2);
+    }
+#undef VGPT_ACC_LAUNCH
+    LAUNCH_OK("vgpt_grad_accumulate");
 }

@@ -216,6 +216,24 @@ def adamw_step(master, param, grad, m, v, lr, beta1, beta2, eps, weight_decay, s
          _ptr(grad_scale), _stream())
 
 
+def adamw_ema_step(master, param, grad, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale, ema, ema_decay):
+    """adamw_step that also moves the fp32 EMA of the master weights in the same pass (vgpt_adamw_ema_step)."""
+    _chk(ema, F32, "adamw_ema_step.ema")
+    if ema.numel() != master.numel():
+        raise VgptError("adamw_ema_step: ema and master differ in length")
+    call("vgpt_adamw_ema_step", master.data_ptr(), param.data_ptr(), grad.data_ptr(), _f32flag(grad), m.data_ptr(),
+         v.data_ptr(), master.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+         _ptr(grad_scale), ema.data_ptr(), float(ema_decay), _stream())
+
+
+def grad_accumulate(acc, grad, mode):
+    """mode 0: acc = float(grad); 1: acc += float(grad); 2: grad = T(acc + float(grad)), acc untouched (vgpt_grad_accumulate)."""
+    _chk(acc, F32, "grad_accumulate.acc")
+    if not grad.is_cuda or not grad.is_contiguous() or grad.numel() != acc.numel():
+        raise VgptError("grad_accumulate: grad must be a contiguous GPU tensor of acc's length")
+    call("vgpt_grad_accumulate", acc.data_ptr(), grad.data_ptr(), _f32flag(grad), acc.numel(), int(mode), _stream())
+
+
 def linear_dx(dy2d, weight, scratch=None, dres=None, out=None):
     """dX (M, K) = dY (M, N) @ W (N, K) (+ dres): the weight is read as the transposed operand of the GEMM
     (include/vgpt.h, vgpt_gemm_bf16_tr); `scratch` is unused (kept for callers of the transposing version)."""

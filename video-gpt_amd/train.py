@@ -19,10 +19,15 @@ optimizer to DeepSpeed's bf16 AdamW (fp32 master weights).  Here:
     folded into the AdamW kernel's gradient scale (no separate pass over the gradients);
   * lora_rank=r (train_x1_stage1_noiseinput.py:204-223) freezes the base model and trains rank-r adapters on qkv_proj /
     o_proj through the three products of ops_lora.py: no dW GEMM, no base optimizer state, one small bucket to exchange
-    (DESIGN.md §6a).
+    (DESIGN.md §6a);
+  * gradient_accumulation_steps=A keeps one fp32 accumulator per gradient bucket and adds every micro-step's bucket to it
+    right where the bucket would be exchanged; the last micro-step writes the once-rounded sum back into the bucket and the
+    exchange, clip and AdamW run on it unchanged, 1/A folded in where 1/world is.  use_ema=True keeps an fp32 EMA of the
+    fp32 master weights, moved inside the AdamW launch (vgpt_adamw_ema_step); DESIGN.md §6b.
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 
@@ -40,6 +45,8 @@ from .ops import BF16, VgptError
 
 F32 = torch.float32
 DP_SHARDING_MODES = ("none", "optimizer")
+LR_SCHEDULERS = ("constant", "constant_with_warmup", "linear", "cosine", "cosine_with_restarts", "polynomial")
+LR_END = 1e-7           # end LR of "polynomial" (get_scheduler passes none: the schedule's own default)
 LORA_TARGETS = ("qkv_proj", "o_proj")
 
 
@@ -62,6 +69,50 @@ def shard_partition(n: int, world: int):
     g = world * SHARD_GRANULE
     padded = -(-n // g) * g
     return padded, padded // world
+
+
+def lr_factor(name: str, k: int, warmup: int = 0, total: Optional[int] = None, num_cycles: Optional[float] = None,
+              power: float = 1.0, base_lr: float = 1.0) -> float:
+    """Multiplier of the base LR at scheduler step k (k = 0 for the first optimizer step): the lambdas diffusers'
+    get_scheduler(name, num_warmup_steps=warmup, num_training_steps=total, num_cycles=..., power=...) hands LambdaLR
+    (train_x1_stage1_noiseinput.py:279-283, 513-521), restated.  Every name but "constant" ramps k / max(1, warmup) while
+    k < warmup.  Past it, with progress = (k - warmup) / max(1, total - warmup):
+      linear                max(0, (total - k) / max(1, total - warmup))
+      cosine                max(0, (1 + cos(2 pi num_cycles progress)) / 2), num_cycles 0.5 by default
+      cosine_with_restarts  0 once progress >= 1, else max(0, (1 + cos(pi ((num_cycles progress) mod 1))) / 2), default 1
+      polynomial            ((base_lr - LR_END) (1 - (k - warmup) / (total - warmup))^power + LR_END) / base_lr, and
+                            LR_END / base_lr once k > total (the only schedule that needs base_lr)
+    Pure Python in float64; no GPU, no torch."""
+    if name not in LR_SCHEDULERS:
+        raise VgptError(f"lr_scheduler {name!r}: built are {LR_SCHEDULERS}")
+    k, warmup = int(k), int(warmup)
+    if name == "constant":
+        return 1.0
+    if k < warmup:
+        return float(k) / float(max(1, warmup))
+    if name == "constant_with_warmup":
+        return 1.0
+    if total is None:
+        raise VgptError(f"lr_scheduler {name!r} needs lr_num_training_steps")
+    total = int(total)
+    if name == "linear":
+        return max(0.0, float(total - k) / float(max(1, total - warmup)))
+    progress = float(k - warmup) / float(max(1, total - warmup))
+    if name == "cosine":
+        cycles = 0.5 if num_cycles is None else float(num_cycles)
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * cycles * 2.0 * progress)))
+    if name == "cosine_with_restarts":
+        cycles = 1.0 if num_cycles is None else float(num_cycles)
+        if progress >= 1.0:
+            return 0.0
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * ((cycles * progress) % 1.0))))
+    # polynomial
+    if not base_lr > LR_END:
+        raise VgptError(f"lr_scheduler 'polynomial': the base LR {base_lr} must exceed the end LR {LR_END}")
+    if k > total:
+        return LR_END / base_lr
+    remaining = 1.0 - (k - warmup) / (total - warmup) if total > warmup else 0.0
+    return ((base_lr - LR_END) * remaining ** power + LR_END) / base_lr
 
 
 _TRAINER_OF = weakref.WeakKeyDictionary()   # model -> weakref to the trainer whose optimizer updates it on a stream of its own
@@ -88,15 +139,24 @@ class Stage1Trainer:
                  lr_scheduler: str = "constant", lr_warmup_steps: int = 0, gradient_checkpointing: Optional[bool] = None,
                  forward_only: bool = False, lr_scheduler_steps_per_optimizer_step: int = 1,
                  overlap_optimizer: bool = False, dp_sharding: Optional[str] = None, lora_rank: Optional[int] = None,
-                 lora_alpha: Optional[float] = None, lora_target_modules=LORA_TARGETS):
-        """lr_scheduler / lr_warmup_steps: diffusers' get_scheduler("constant" | "constant_with_warmup")
-        (train_x1_stage1_noiseinput.py:279-283; the scripts use constant_with_warmup): the k-th optimizer step (k = 0, 1,
-        ...) runs at lr * min(1, k * lr_scheduler_steps_per_optimizer_step / warmup).
+                 lora_alpha: Optional[float] = None, lora_target_modules=LORA_TARGETS,
+                 gradient_accumulation_steps: int = 1, use_ema: bool = False, ema_decay: float = 0.9999,
+                 lr_num_training_steps: Optional[int] = None, lr_num_cycles: Optional[float] = None,
+                 lr_power: float = 1.0):
+        """lr_scheduler / lr_warmup_steps / lr_num_training_steps / lr_num_cycles / lr_power: diffusers' get_scheduler
+        (train_x1_stage1_noiseinput.py:279-283, 513-521; the scripts use constant_with_warmup), one of LR_SCHEDULERS: the
+        k-th optimizer step (k = 0, 1, ...) runs at lr * lr_factor(name, k * lr_scheduler_steps_per_optimizer_step, ...);
+        "constant_with_warmup" is lr * min(1, k * stride / warmup).  "linear", "cosine", "cosine_with_restarts" and
+        "polynomial" need lr_num_training_steps (counted like the warm-up, in scheduler steps); lr_num_cycles defaults to
+        0.5 (cosine) / 1 (restarts), lr_power to 1.0 with end LR 1e-7: get_scheduler's defaults.
         Stepping convention mirrored (default 1 = the reference's scripts: they pass --deepspeed_plugin
         (pretrain_stage1_nv.sh:49), so `accelerator.prepare` wraps the scheduler in accelerate's DeepSpeedSchedulerWrapper
         whose step() is a no-op and the DeepSpeed engine advances it ONCE per optimizer step whatever the world size;
         num_warmup_steps there is lr_warmup_steps * gradient_accumulation_steps, :279-283, and the scripts use
-        accumulation 1).  Without the DeepSpeed plugin accelerate's AcceleratedScheduler advances the schedule
+        accumulation 1.  With gradient_accumulation_steps = A > 1 the schedule here still counts OPTIMIZER steps: micro-steps
+        do not advance it.  The reference under DeepSpeed also advances once per optimizer step but passes
+        num_warmup_steps = lr_warmup_steps * A, so its warm-up lasts A times as many optimizer steps: pass
+        lr_warmup_steps = A * that value to mirror it; no default changes).  Without the DeepSpeed plugin accelerate's AcceleratedScheduler advances the schedule
         `num_processes` times per optimizer step (split_batches=False): pass lr_scheduler_steps_per_optimizer_step =
         world size to mirror that launch instead.  No fixture pins the LR trajectory of the reference's loop (it needs
         deepspeed, absent here): parity of the warm-up length is unpinned.  gradient_checkpointing (default: model.llm.gradient_checkpointing, set by
@@ -108,16 +168,54 @@ class Stage1Trainer:
         updated parameters).  Inert at world size 1.  lora_rank = r (1 <= r <= 64; train...py:204-223): the
         base model is frozen and rank-r adapters on lora_target_modules of every decoder layer are the only trained tensors
         (lora_alpha defaults to r; peft's "gaussian" init); no base gradient buckets, masters or moments exist, the adapter
-        state is a few MB and is never sharded."""
+        state is a few MB and is never sharded.
+        gradient_accumulation_steps = A (--gradient_accumulation_steps, train...py:121, 353, 393-413): step(update=True)
+        counts micro-steps; micro-steps 1 .. A-1 run forward and backward and add every gradient bucket to an fp32
+        accumulator of its own (full length also when sharded, allocated on first use, 4 B per parameter) with no
+        collective, no clip, no AdamW and no change of step_count or the LR; micro-step A writes bucket = T(acc + bucket)
+        (one rounding of the fp32 sum), exchanges it as ever and steps the optimizer.  The factor 1/A goes where 1/world
+        goes, into clip_coef: the clip acts on the norm of the MEAN gradient over micro-batches and ranks and AdamW sees the
+        mean, as accelerate's loss / A with clipping on sync_gradients only (:393-400).  `grad_norm` holds the norm of the
+        SUM over the A micro-batches and the ranks (A * world times the norm of the mean), as it holds the sum over ranks
+        at A = 1.  step(update=False) stays a stand-alone backward that overwrites the buckets and touches neither the
+        accumulators nor the micro-step counter (legal in the middle of a cycle).
+        use_ema / ema_decay (--use_ema, :227-230, 288-290, 406-408, 440-447; update_ema, LVM/utils.py:27-34, decay 0.9999):
+        one fp32 EMA buffer per master buffer (this rank's shard when sharded), a copy of the master at construction (the
+        reference's update_ema(ema, model, decay=0)), moved inside every AdamW launch: ema = d ema + (1 - d) master_new.
+        Deliberate difference: the reference's EMA is a deepcopy of the model in the model's dtype, and under bf16
+        parameters an increment of relative size 1 - 0.9999 lies below bf16 resolution, so that EMA barely moves; here the
+        EMA is fp32 and follows the fp32 master.  Full fine-tuning only.  ema_state_dict() / ema_weights() read it."""
         model._check_ready()
         if hasattr(model, "release_engines"):
             model.release_engines()          # a sampler engine cached on the model holds GBs the trainer's buffers want
         self.model = model
         self.cfg = model.llm.config
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
-        if lr_scheduler not in ("constant", "constant_with_warmup"):
-            raise VgptError(f"lr_scheduler {lr_scheduler!r}: only 'constant' and 'constant_with_warmup' are built")
+        if lr_scheduler not in LR_SCHEDULERS:
+            raise VgptError(f"lr_scheduler {lr_scheduler!r}: built are {LR_SCHEDULERS}")
+        if lr_scheduler not in ("constant", "constant_with_warmup") and lr_num_training_steps is None:
+            raise VgptError(f"lr_scheduler {lr_scheduler!r} needs lr_num_training_steps")
         self.lr_scheduler, self.lr_warmup_steps = lr_scheduler, int(lr_warmup_steps)
+        self.lr_num_training_steps = None if lr_num_training_steps is None else int(lr_num_training_steps)
+        self.lr_num_cycles = None if lr_num_cycles is None else float(lr_num_cycles)
+        self.lr_power = float(lr_power)
+        A = gradient_accumulation_steps
+        if isinstance(A, bool) or not isinstance(A, int) or A < 1:
+            raise VgptError(f"gradient_accumulation_steps {A!r}: an integer >= 1 is built")
+        self.accum_steps = A
+        self._micro = 0              # micro-steps taken in the current accumulation cycle
+        self._acc = None             # fp32 accumulators (small | lora, [layer 0 .. nl-1]); allocated on first use
+        self.use_ema, self.ema_decay = bool(use_ema), float(ema_decay)
+        self.ema_small, self.ema_layers = None, None
+        self._ema_swapped = False    # inside ema_weights(): the parameter buffers hold the EMA, not the training weights
+        self.last_load = None        # what the last load_checkpoint did with the EMA ({"ema": ...}); None before any load
+        if self.use_ema:
+            if lora_rank is not None:
+                raise VgptError("use_ema with lora_rank: EMA of adapters is not built")
+            if forward_only:
+                raise VgptError("use_ema with forward_only: there is no optimizer state, EMA of a forward-only trainer is not built")
+            if not 0.0 <= self.ema_decay <= 1.0:
+                raise VgptError(f"ema_decay {ema_decay!r}: expected 0 <= decay <= 1")
         if int(lr_scheduler_steps_per_optimizer_step) < 1:
             raise VgptError("lr_scheduler_steps_per_optimizer_step must be >= 1")
         self.lr_sched_stride = int(lr_scheduler_steps_per_optimizer_step)
@@ -233,6 +331,7 @@ class Stage1Trainer:
         self.param_small = flat
         bump_weight_generation(model)     # storage re-pointed; from here on the optimizer writes it through raw pointers
         self._init_scalars()
+        self._init_ema()
 
     # ---- LoRA mode --------------------------------------------------------------------------------------------------
     def _init_lora(self, r: int, alpha, targets):
@@ -279,11 +378,11 @@ class Stage1Trainer:
         if train:
             self._init_scalars()
 
-    def _lora_optimizer_step(self, lr, b1, b2):
+    def _lora_optimizer_step(self, lr, b1, b2, micro_batches=1):
         """sumsq, clip coefficient and AdamW over the one adapter bucket (the caller has advanced the step counter)."""
         self.sumsq.zero_()
         T.sumsq(self.lora_bucket, self.sumsq)
-        w = float(self.world)
+        w = float(self.world * micro_batches)
         T.clip_coef(self.sumsq, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w)
         if not self.overlap_optimizer:
             T.adamw_step(self.lora_master, self.lora_param, self.lora_bucket, self.lora_m, self.lora_v, lr, b1, b2, self.eps,
@@ -329,6 +428,39 @@ class Stage1Trainer:
                 bump_weight_generation(self.model)
         return cm()
 
+    def _init_ema(self):
+        """update_ema(ema, model, decay=0) (train...py:288-290): the EMA starts as a copy of the fp32 master weights."""
+        if self.use_ema:
+            self.ema_layers = [t.clone() for t in self.master_layers]
+            self.ema_small = self.master_small.clone()
+
+    def _adamw(self, master, param, grad, m_, v_, ema, lr, b1, b2):
+        """One AdamW launch over a flat bucket; with an EMA buffer the launch that also moves it (no second pass)."""
+        if ema is None:
+            T.adamw_step(master, param, grad, m_, v_, lr, b1, b2, self.eps, self.wd, self.step_count, self.coef)
+        else:
+            T.adamw_ema_step(master, param, grad, m_, v_, lr, b1, b2, self.eps, self.wd, self.step_count, self.coef, ema,
+                             self.ema_decay)
+
+    # ---- gradient accumulation ---------------------------------------------------------------------------------------
+    def _accum_mode(self, update: bool):
+        """None: no accumulation in this call (A == 1, or a stand-alone backward); else vgpt_grad_accumulate's mode of this
+        micro-step: 0 first, 1 middle, 2 last (the bucket receives the sum and the optimizer steps)."""
+        if not update or self.accum_steps == 1:
+            return None
+        if self._micro == self.accum_steps - 1:
+            return 2
+        return 0 if self._micro == 0 else 1
+
+    def _accumulators(self):
+        if self._acc is None:
+            z = lambda t: torch.empty(t.numel(), dtype=F32, device=self.dev)
+            if self.lora_rank is not None:
+                self._acc = (z(self.lora_bucket), [])
+            else:
+                self._acc = (z(self.small_bucket), [z(b) for b in self.layer_buckets])
+        return self._acc
+
     def _init_scalars(self):
         self.sumsq = torch.zeros(1, dtype=F32, device=self.dev)
         self.coef = torch.ones(1, dtype=F32, device=self.dev)
@@ -371,6 +503,7 @@ class Stage1Trainer:
         self.m_small, self.v_small = z(self.master_small), z(self.master_small)
         bump_weight_generation(self.model)
         self._init_scalars()
+        self._init_ema()
         self._partials = torch.zeros(self.world, dtype=F32, device=self.dev)   # every rank's sum of squares, rank order
 
     def _reduce(self, bucket):
@@ -403,9 +536,12 @@ class Stage1Trainer:
         """Learning rate of the NEXT optimizer step (diffusers get_constant_schedule_with_warmup's lambda at
         current_step = optimizer steps taken so far)."""
         k = self.step_count * self.lr_sched_stride
-        if self.lr_scheduler == "constant_with_warmup" and k < self.lr_warmup_steps:
-            return self.lr * k / max(1.0, float(self.lr_warmup_steps))
-        return self.lr
+        if self.lr_scheduler in ("constant", "constant_with_warmup"):      # the two first built: their expression, to the bit
+            if self.lr_scheduler == "constant_with_warmup" and k < self.lr_warmup_steps:
+                return self.lr * k / max(1.0, float(self.lr_warmup_steps))
+            return self.lr
+        return self.lr * lr_factor(self.lr_scheduler, k, self.lr_warmup_steps, self.lr_num_training_steps,
+                                   self.lr_num_cycles, self.lr_power, self.lr)
 
     # ------------------------------------------------------------------------------------------------
     def _buf(self, name, shape, dtype=BF16):
@@ -445,7 +581,11 @@ class Stage1Trainer:
              x0_in: Optional[torch.Tensor], t_in: Optional[torch.Tensor], update: bool = True, backward: bool = True,
              input_output_return: bool = False):
         """One optimisation step.  x1/x0: (F, C, h, w) fp32 target latents / noise, t: (F,) fp32;
-        clean/x0_in/t_in: the clean-frame latents and their noise (loss.py:166-192).  Returns the per-frame losses."""
+        clean/x0_in/t_in: the clean-frame latents and their noise (loss.py:166-192).  Returns the per-frame losses.
+        With gradient_accumulation_steps = A > 1 and update=True this is one MICRO-step: the optimizer steps on every A-th
+        call (see __init__)."""
+        if update:
+            self._refuse_inside_ema_weights("step(update=True)")
         m, cfg = self.model, self.cfg
         prep = self._prepare(batch)
         # the previous step's update may still be running on its own stream, its all-gathers (sharded) still in flight
@@ -558,10 +698,12 @@ class Stage1Trainer:
             if update:
                 raise VgptError("Stage1Trainer.step: an optimizer step needs the backward pass")
             return loss
+        acc_mode = self._accum_mode(update)
+        exchange = acc_mode in (None, 2)     # micro-steps before the last issue no collective
         if lora:
             self._lora_backward(locals())
             if update:
-                self.optimizer_step()
+                self._finish_micro_step(acc_mode)
             return loss
         # ---------------- backward ----------------
         g = self.grads
@@ -617,7 +759,9 @@ class Stage1Trainer:
             T.rmsnorm_bwd(hbuf[li], layer.input_layernorm.weight, dn, dh,
                           g[f"llm.layers.{li}.input_layernorm.weight"], layer.input_layernorm.variance_epsilon,
                           dres=dh_b)                                                     # dh (layer input)
-            if self.world > 1 and not self.skip_allreduce and self.overlap_allreduce:
+            if acc_mode is not None:     # right behind this layer's last dW, where its bucket is complete
+                T.grad_accumulate(self._accumulators()[1][li], self.layer_buckets[li], acc_mode)
+            if exchange and self.world > 1 and not self.skip_allreduce and self.overlap_allreduce:
                 handles.append(self._reduce(self.layer_buckets[li]))
         # heads fed by dseq = dh
         dseq = dh
@@ -627,7 +771,9 @@ class Stage1Trainer:
         if cl is not None:
             self._patch_bwd("input_x_embedder", T.gather_rows(dseq, prep["c_rows"], ntok), cl)
         T.embed_bwd(prep["ids"].view(-1), prep["keep"], dseq, g["llm.embed_tokens.weight"])
-        if self.world > 1 and not self.skip_allreduce:
+        if acc_mode is not None:
+            T.grad_accumulate(self._accumulators()[0], self.small_bucket, acc_mode)
+        if exchange and self.world > 1 and not self.skip_allreduce:
             if not self.overlap_allreduce:
                 handles += [self._reduce(b) for b in reversed(self.layer_buckets)]
             handles.append(self._reduce(self.small_bucket))
@@ -635,8 +781,18 @@ class Stage1Trainer:
                 if hd_ is not None:
                     hd_.wait()
         if update:
-            self.optimizer_step()
+            self._finish_micro_step(acc_mode)
         return loss
+
+    def _finish_micro_step(self, acc_mode):
+        """End of a step(update=True): the optimizer steps unless this was a micro-step before the last of its cycle."""
+        if acc_mode is None:
+            self.optimizer_step()
+        elif acc_mode == 2:
+            self._micro = 0
+            self.optimizer_step(micro_batches=self.accum_steps)
+        else:
+            self._micro += 1
 
     def _lora_backward(self, f):
         """Backward with the base frozen: the dX chain of the full backward without a single dW GEMM, and per adapted
@@ -698,8 +854,10 @@ class Stage1Trainer:
                 LO.lora_up_add(dn, du, w["A"], s_is_rp_by_n=True)
             T.rmsnorm_bwd(hbuf[li], layer.input_layernorm.weight, dn, dh, dgain, layer.input_layernorm.variance_epsilon,
                           dres=dh_b)                                                     # dh (layer input)
-        if self.world > 1 and not self.skip_allreduce:
-            dist.all_reduce(self.lora_bucket)        # one small exchange per step
+        if f["acc_mode"] is not None:
+            T.grad_accumulate(self._accumulators()[0], self.lora_bucket, f["acc_mode"])
+        if f["exchange"] and self.world > 1 and not self.skip_allreduce:
+            dist.all_reduce(self.lora_bucket)        # one small exchange per optimizer step
 
     def _neg_sin(self, prep):
         key = ("nsin", prep["rope"][1].data_ptr())
@@ -724,7 +882,11 @@ class Stage1Trainer:
         T.colsum(dtok, g[f"{prefix}.proj.bias"])
 
     # ------------------------------------------------------------------------------------------------
-    def optimizer_step(self):
+    def optimizer_step(self, micro_batches: int = 1):
+        """sumsq, clip coefficient and AdamW on what the gradient buckets hold.  micro_batches: how many micro-batches were
+        summed into them (step() passes gradient_accumulation_steps on the last micro-step): 1 / (world * micro_batches)
+        is folded into the clip coefficient, so AdamW sees the mean gradient."""
+        self._refuse_inside_ema_weights("optimizer_step")
         # an update still running on the optimizer's stream (overlap_optimizer) reads self.coef / self.sumsq and writes the
         # master weights and moments this call is about to touch: wait for it (free in the normal flow, where the forward of
         # the step that produced these gradients already waited for every layer's event)
@@ -736,7 +898,7 @@ class Stage1Trainer:
         self.last_lr = lr
         self.step_count += 1
         if self.lora_rank is not None:
-            self._lora_optimizer_step(lr, *self.betas)
+            self._lora_optimizer_step(lr, *self.betas, micro_batches=micro_batches)
             return
         self.sumsq.zero_()
         for b in self.layer_buckets:
@@ -747,19 +909,22 @@ class Stage1Trainer:
             # every rank's sum over its reduced shards, in rank order, added on the device in a fixed order by clip_coef:
             # every rank computes the same norm and coefficient
             partials = SPM.all_gather_flat(self.sumsq, self._group, out=self._partials).view(-1)
-        w = float(self.world)
-        # norm of the AVERAGED gradient = norm(sum)/world; coefficient already carries the 1/world factor
+        w = float(self.world * micro_batches)
+        # norm of the AVERAGED gradient = norm(sum)/world; coefficient already carries the 1/world factor (and 1/A, when the
+        # buckets hold the sum over A micro-batches)
         T.clip_coef(partials, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w)
         b1, b2 = self.betas
         if self._sharded:
             self._sharded_update(lr, b1, b2)
             return
+        ema_l = self.ema_layers if self.use_ema else [None] * len(self.layer_buckets)
+        ema_s = self.ema_small if self.use_ema else None
         if not self.overlap_optimizer:
             for i in range(len(self.layer_buckets)):
-                T.adamw_step(self.master_layers[i], self.param_layers[i], self.layer_buckets[i], self.m_layers[i],
-                             self.v_layers[i], lr, b1, b2, self.eps, self.wd, self.step_count, self.coef)
-            T.adamw_step(self.master_small, self.param_small, self.small_bucket, self.m_small, self.v_small, lr, b1, b2,
-                         self.eps, self.wd, self.step_count, self.coef)
+                self._adamw(self.master_layers[i], self.param_layers[i], self.layer_buckets[i], self.m_layers[i],
+                            self.v_layers[i], ema_l[i], lr, b1, b2)
+            self._adamw(self.master_small, self.param_small, self.small_bucket, self.m_small, self.v_small, ema_s,
+                        lr, b1, b2)
             return
         # The update is a pure HBM stream (28 bytes per parameter) and the next step's forward is matrix work: they run side by
         # side.  Everything below goes to the optimizer's stream behind the clip coefficient; the small bucket (embeddings,
@@ -770,14 +935,14 @@ class Stage1Trainer:
         ready.record(main)
         self._opt_stream.wait_event(ready)
         with torch.cuda.stream(self._opt_stream):
-            T.adamw_step(self.master_small, self.param_small, self.small_bucket, self.m_small, self.v_small, lr, b1, b2,
-                         self.eps, self.wd, self.step_count, self.coef)
+            self._adamw(self.master_small, self.param_small, self.small_bucket, self.m_small, self.v_small, ema_s,
+                        lr, b1, b2)
             ev_small = torch.cuda.Event()
             ev_small.record(self._opt_stream)
             evs = []
             for i in range(len(self.layer_buckets)):
-                T.adamw_step(self.master_layers[i], self.param_layers[i], self.layer_buckets[i], self.m_layers[i],
-                             self.v_layers[i], lr, b1, b2, self.eps, self.wd, self.step_count, self.coef)
+                self._adamw(self.master_layers[i], self.param_layers[i], self.layer_buckets[i], self.m_layers[i],
+                            self.v_layers[i], ema_l[i], lr, b1, b2)
                 e = torch.cuda.Event()
                 e.record(self._opt_stream)
                 evs.append(e)
@@ -793,13 +958,14 @@ class Stage1Trainer:
             ready = torch.cuda.Event()
             ready.record(torch.cuda.current_stream())
             self._opt_stream.wait_event(ready)
-        buckets = [(self.master_small, self.param_small, self.small_bucket, self.m_small, self.v_small)]
-        buckets += list(zip(self.master_layers, self.param_layers, self.layer_buckets, self.m_layers, self.v_layers))
+        ema_l = self.ema_layers if self.use_ema else [None] * len(self.layer_buckets)
+        ema_s = self.ema_small if self.use_ema else None
+        buckets = [(self.master_small, self.param_small, self.small_bucket, self.m_small, self.v_small, ema_s)]
+        buckets += list(zip(self.master_layers, self.param_layers, self.layer_buckets, self.m_layers, self.v_layers, ema_l))
         evs, works = [], []
         with torch.cuda.stream(self._opt_stream if ov else torch.cuda.current_stream()):
-            for master, param, grad, m_, v_ in buckets:
-                T.adamw_step(master, self._shard(param), self._shard(grad), m_, v_, lr, b1, b2, self.eps, self.wd,
-                             self.step_count, self.coef)
+            for master, param, grad, m_, v_, ema in buckets:
+                self._adamw(master, self._shard(param), self._shard(grad), m_, v_, ema, lr, b1, b2)
                 works.append(None if self.skip_allreduce else
                              SPM.all_gather_flat(self._shard(param), self._group, out=param, async_op=True))
                 if ov:
@@ -837,9 +1003,93 @@ class Stage1Trainer:
                       (self.v_layers[i], f"v.{i}", n)]
         return pairs
 
+    def _ema_tensors(self):
+        """_optimizer_tensors' triples of the EMA buffers (none without use_ema): ema_small / ema.{i} beside master.*."""
+        if not self.use_ema:
+            return []
+        return [(self.ema_small, "ema_small", self._small_numel)] + \
+               [(self.ema_layers[i], f"ema.{i}", n) for i, n in enumerate(self._bucket_numel)]
+
+    def _schedule_record(self):
+        return {"lr_scheduler": self.lr_scheduler, "lr_warmup_steps": self.lr_warmup_steps,
+                "lr_num_training_steps": self.lr_num_training_steps, "lr_num_cycles": self.lr_num_cycles,
+                "lr_power": self.lr_power, "gradient_accumulation_steps": self.accum_steps}
+
+    # ---- EMA weights -------------------------------------------------------------------------------------------------
+    def _ema_flat(self, t):
+        """The whole (padded) fp32 EMA bucket of which `t` is this trainer's tensor: gathered when sharded (a collective:
+        every rank calls)."""
+        return SPM.all_gather_flat(t, self._group).view(-1) if self._sharded else t
+
+    def _ema_buckets(self):
+        """(EMA tensor, flat bf16 parameter buffer, parameter names in buffer order) per bucket, the small one first."""
+        if not self.use_ema:
+            raise VgptError("this trainer keeps no EMA (use_ema=False)")
+        return [(self.ema_small, self.param_small, self.small_names)] + \
+               list(zip(self.ema_layers, self.param_layers, self.layer_names))
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The EMA weights as a bf16 state dict under the reference's parameter keys (what train...py:440-447 saves from
+        ema.state_dict()): every parameter is the fp32 EMA rounded once to bf16; entries of the model's state dict that
+        are not trained parameters are copied as they are.  A sharded EMA is gathered (every rank calls)."""
+        self.finish_optimizer()
+        out = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        for ema, _, names in self._ema_buckets():
+            full = self._ema_flat(ema)
+            o = 0
+            for k in names:
+                sz = self.params[k].numel()
+                if k in out:
+                    out[k] = full[o:o + sz].view(self.params[k].shape).to(BF16)
+                o += sz
+        return out
+
+    def ema_weights(self):
+        """Context manager for sampling from the EMA weights mid-training, built like merged_weights(): inside it the
+        model's parameters hold bf16(EMA); on exit the training weights come back bit for bit.  The flat param_* buffers
+        AdamW writes through raw pointers stay where they are: the values are copied in and out, nothing is re-pointed.
+        Cached sampler engines refold on both edges (weight generation bumped).  Sharded: every rank enters together.
+        Inside, step(update=True), optimizer_step() and save_checkpoint() raise: they would train on, or save, the EMA
+        values as the model's weights, and the exit would then put stale training weights back.  Forward-only and
+        stand-alone backward calls (update=False) are allowed: they evaluate the EMA weights.  Not re-entrant."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            buckets = self._ema_buckets()
+            if self._ema_swapped:
+                raise VgptError("ema_weights: already inside the context")
+            self.finish_optimizer()
+            saved = [param.detach().clone() for _, param, _ in buckets]
+            self._ema_swapped = True
+            try:
+                with torch.no_grad():
+                    for ema, param, _ in buckets:
+                        param.copy_(self._ema_flat(ema))     # fp32 -> bf16, round to nearest even
+                bump_weight_generation(self.model)
+                yield self.model
+            finally:
+                with torch.no_grad():
+                    for (_, param, _), sv_ in zip(buckets, saved):
+                        param.copy_(sv_)
+                self._ema_swapped = False
+                bump_weight_generation(self.model)
+        return cm()
+
+    def _refuse_inside_ema_weights(self, what: str):
+        if self._ema_swapped:
+            raise VgptError(f"{what} inside ema_weights(): the model holds the EMA weights, not the training weights")
+
     def save_checkpoint(self, results_dir: str, global_step: Optional[int] = None) -> str:
         """Rank 0 writes (replicas are identical under data parallelism; a sharded optimizer state is gathered to it one
-        bucket at a time through host memory, in the replicated layout); every rank returns after the files exist."""
+        bucket at a time through host memory, in the replicated layout); every rank returns after the files exist.
+        With use_ema the optimizer file gains ema_small / ema.{i} and the directory ema.safetensors, the bf16
+        ema_state_dict() (train...py:440-447).  In the middle of an accumulation cycle it raises: the accumulators are not
+        part of a checkpoint, and the reference saves on cycle boundaries only (:437)."""
+        self._refuse_inside_ema_weights("save_checkpoint")
+        if self._micro != 0:
+            raise VgptError(f"save_checkpoint in the middle of an accumulation cycle (micro-step {self._micro} of "
+                            f"{self.accum_steps}): checkpoints are written on optimizer-step boundaries")
         self.finish_optimizer()
         import json
         import os
@@ -855,7 +1105,8 @@ class Stage1Trainer:
                 dist.barrier()
             return path
         opt = {}
-        for t, key, n in self._optimizer_tensors():
+        ema_sd = self.ema_state_dict() if self.use_ema else None     # gathers when sharded: every rank takes part
+        for t, key, n in self._optimizer_tensors() + self._ema_tensors():
             if self._sharded:     # every rank takes part; one gathered bucket on the device at a time, then host memory
                 full = SPM.all_gather_flat(t, self._group).view(-1)[:n]
                 if writer:
@@ -868,10 +1119,12 @@ class Stage1Trainer:
             save_file({k: v.detach().cpu().contiguous() for k, v in self.model.state_dict().items()},
                       os.path.join(path, "model.safetensors"))
             save_file(opt, os.path.join(path, "optimizer.safetensors"))
+            if ema_sd is not None:
+                save_file({k: v.detach().cpu().contiguous() for k, v in ema_sd.items()}, os.path.join(path, "ema.safetensors"))
             with open(os.path.join(path, "trainer_state.json"), "w") as f:
                 json.dump({"step_count": self.step_count, "global_step": step, "lr": self.lr, "weight_decay": self.wd,
-                           "betas": list(self.betas), "eps": self.eps, "lr_scheduler": self.lr_scheduler,
-                           "lr_warmup_steps": self.lr_warmup_steps, "small_names": self.small_names}, f)
+                           "betas": list(self.betas), "eps": self.eps, **self._schedule_record(),
+                           "use_ema": self.use_ema, "ema_decay": self.ema_decay, "small_names": self.small_names}, f)
         if distributed:
             dist.barrier()
         return path
@@ -882,7 +1135,10 @@ class Stage1Trainer:
         The optimizer state is stored unpadded and unsharded: a sharded trainer copies its own slice, so checkpoints move
         between dp_sharding modes and world sizes.  Only checkpoints written by this trainer resume (the reference's are accelerate / DeepSpeed `save_state`
         directories, whose optimizer shards are pickles: warm-start from those through LVM.from_pretrained's weight
-        loaders instead)."""
+        loaders instead).  EMA: a checkpoint without EMA tensors loaded into a use_ema trainer starts the EMA as a copy of
+        the loaded master weights (recorded in `self.last_load["ema"]` and logged); an EMA checkpoint loaded into a trainer
+        without EMA ignores them.  The checkpoint's gradient_accumulation_steps is a record only: resuming with another
+        value is allowed, the optimizer state does not depend on it.  An accumulation cycle under way is dropped."""
         self.finish_optimizer()
         import json
         import os
@@ -891,13 +1147,19 @@ class Stage1Trainer:
             st = json.load(f)
         if (self.lora_rank is not None) != ("lora" in st):
             raise VgptError(f"{path}: a LoRA checkpoint resumes a LoRA trainer and a full one a full trainer")
+        self._refuse_inside_ema_weights("load_checkpoint")
         if self.lora_rank is not None:
             self._load_lora(path, st)
+            self.last_load = {"ema": "none"}
             return self._restore_record(st, restore_hyperparameters)
         if st["small_names"] != self.small_names:
             raise VgptError("checkpoint was written for a different parameter layout")
         opt = load_file(os.path.join(path, "optimizer.safetensors"))
         pairs = self._optimizer_tensors()
+        ema_pairs = self._ema_tensors()
+        ema_in_file = bool(ema_pairs) and any(k in opt for _, k, _ in ema_pairs)
+        if ema_in_file:
+            pairs = pairs + ema_pairs                    # validated and copied like the rest
         model_sd = load_file(os.path.join(path, "model.safetensors"))
         own = self.model.state_dict()
         problems = [f"optimizer tensor {k} missing" for _, k, _ in pairs if k not in opt]
@@ -917,6 +1179,13 @@ class Stage1Trainer:
             dst.zero_()
             if hi > lo:
                 dst[:hi - lo].copy_(opt[key][lo:hi])
+        self.last_load = {"ema": "none" if not ema_pairs else "restored" if ema_in_file else "initialised from master"}
+        if ema_pairs and not ema_in_file:
+            import logging
+            for ema, master in zip([self.ema_small] + self.ema_layers, [self.master_small] + self.master_layers):
+                ema.copy_(master)
+            logging.getLogger(__name__).warning("%s holds no EMA tensors: the EMA starts as a copy of the loaded master weights",
+                                                path)
         with torch.no_grad():     # parameters are views of the flat bf16 buffers: copy in place, keep the views
             for k, p_ in own.items():
                 p_.copy_(model_sd[k])
@@ -925,11 +1194,15 @@ class Stage1Trainer:
 
     def _restore_record(self, st, restore_hyperparameters: bool) -> int:
         self.step_count = int(st["step_count"])
+        self._micro = 0
         if restore_hyperparameters:
             self.lr, self.wd, self.eps = float(st["lr"]), float(st["weight_decay"]), float(st["eps"])
             self.betas = tuple(st["betas"])
             self.lr_scheduler = st.get("lr_scheduler", self.lr_scheduler)
             self.lr_warmup_steps = int(st.get("lr_warmup_steps", self.lr_warmup_steps))
+            self.lr_num_training_steps = st.get("lr_num_training_steps", self.lr_num_training_steps)
+            self.lr_num_cycles = st.get("lr_num_cycles", self.lr_num_cycles)
+            self.lr_power = float(st.get("lr_power", self.lr_power))
         return int(st["global_step"])
 
     # LoRA mode: peft's adapter directory (adapter_model.safetensors + adapter_config.json; layout written from knowledge of
@@ -947,8 +1220,7 @@ class Stage1Trainer:
                   os.path.join(path, "optimizer.safetensors"))
         with open(os.path.join(path, "trainer_state.json"), "w") as f:
             json.dump({"step_count": self.step_count, "global_step": step, "lr": self.lr, "weight_decay": self.wd,
-                       "betas": list(self.betas), "eps": self.eps, "lr_scheduler": self.lr_scheduler,
-                       "lr_warmup_steps": self.lr_warmup_steps,
+                       "betas": list(self.betas), "eps": self.eps, **self._schedule_record(),
                        "lora": {"r": self.lora_rank, "rp": self.lora_rp, "lora_alpha": self.lora_alpha,
                                 "target_modules": list(self.lora_targets), "numel": self._lora_numel}}, f)
 
