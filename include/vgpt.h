@@ -122,6 +122,16 @@ int vgpt_gemm_get_family(void);
  * was refused, or had M == 0 (every entry point returns OK for it), leaves none.  A read-only record for tests: it decides nothing.  Like the family switch it is
  * process-wide and not thread-safe: read it right after the call it is meant for. */
 int vgpt_gemm_last_launches(int32_t* out, int cap);
+/* Column order of the four-wave kernel's 256 x 288 tiles under vgpt_gemm_bf16_rope[_prenorm].  Where q, k and v have the same
+ * number of 96-wide heads (head_dim == 96, N % 288 == 0, 3 * rope_cols == 2 * N with rope_cols = n_rot_heads * head_dim), column
+ * tile t computes q head t, k head t and v head t, so that every tile carries the same share of rotated columns.  Each of
+ * the tile's two wave columns (144 slots = 9 sub-tiles of 16) holds: sub-tiles 0-2 q and 3-5 k, pair groups u = 3 * wn + {0, 1, 2}
+ * (slots 0..7 of a sub-tile are d = 8u .. 8u + 7, slots 8..15 their partners d + 48), sub-tiles 6-8 the v columns
+ * 48 * wn .. 48 * wn + 47 of the head.  Returns the output column (= row of W) behind `slot` (0..287) of tile `tile`
+ * (0 .. N / 288 - 1), computed by the function the kernel uses, or -1 where this order does not apply: any other shape (the
+ * kernel then keeps three consecutive heads per tile), a tile or slot out of range.  Host code only: no GPU needed, decides
+ * nothing.  Added without a version bump: no existing signature changed. */
+int64_t vgpt_gemm_rope_grouped_col(int64_t N, int64_t rope_cols, int head_dim, int64_t tile, int slot);
 
 /* RMSNorm folded into the GEMMs around it (a decoder layer's two Phi3RMSNorm calls, OmniGen/transformer.py:196-214 through
  * transformers' Phi3DecoderLayer: hidden = residual + attn(input_layernorm(hidden)); hidden = residual +

@@ -38,6 +38,7 @@ SIGNATURES = {
     "vgpt_gemm_set_family": (c_int, [c_int]),
     "vgpt_gemm_get_family": (c_int, []),
     "vgpt_gemm_last_launches": (c_int, [POINTER(c_int32), c_int]),
+    "vgpt_gemm_rope_grouped_col": (_I64, [_I64, _I64, c_int, _I64, c_int]),
     "vgpt_gemm_norm_workspace_bytes": (_I64, [_I64, _I64, _I64]),
     "vgpt_gemm_bf16_resid_rstd": (c_int, [_P, _P, _P, _P, _P, _P, _I64, c_float, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
     "vgpt_rms_rstd": (c_int, [_P, _P, _I64, _I64, _I64, c_float, _P]),

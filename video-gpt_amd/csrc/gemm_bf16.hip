@@ -82,6 +82,7 @@ struct GemmArgs {
     const float* rope_cos;
     const float* rope_sin;
     int rope_cols, head_dim;
+    int rope_grouped = 0;   // rope_grouped_ok(): 288-wide tiles of the four-wave kernel hold one q, one k and one v head each
     // MODE_GATED, training forward (vgpt_gated_mlp_act_fwd_keep): also store [gate | up] (M, 2I) rounded to bf16 -- what
     // gate_up_proj returns and the backward reads -- and compute act(gate) * up FROM the rounded values, bit for bit what
     // the plain GEMM followed by vgpt_silu_mul_fwd produces; null: inference (activation from the fp32 accumulators)
@@ -160,6 +161,34 @@ __device__ __forceinline__ int rope_col_of_slot(int gs, int rope_cols, int head_
     if (gs >= rope_cols) return gs;
     const int u = gs >> 4, w = gs & 15, per = head_dim >> 4;
     return (u / per) * head_dim + (u % per) * 8 + (w & 7) + ((w & 8) ? (head_dim >> 1) : 0);
+}
+
+// MODE_ROPE: one rotated element, the same three roundings in every kernel and epilogue: own * c + other * s in the upper
+// half-wave (b cos + a sin), own * c - other * s in the lower (a cos - b sin), as fma(own, c, +-rn(other * s)).  Spelled out
+// with contraction off: left to the compiler, `own * c + other * s` became this form in the four-wave epilogues and a mix of
+// it and rn(own * c) +- rn(other * s) inside one quad of gemm_bf16_kernel's, so the two families differed by one bf16 step in
+// about one rotated element of 10^5 (profiles/r13_family_diff_*).
+__device__ __forceinline__ float rope_rotate(float own, float other, float c, float s, bool upper) {
+#pragma clang fp contract(off)
+    const float p = other * s;
+    return __builtin_fmaf(own, c, upper ? p : -p);
+}
+
+// MODE_ROPE, 256 x 288 tiles of the four-wave kernel, head-grouped form: where q, k and v have the same number of 96-wide heads
+// (head_dim 96, 3 rope_cols == 2 N, whole 288-wide tiles) tile `tn` computes q head tn, k head tn and v head tn instead of three
+// consecutive heads of one kind, so every tile -- and both of its wave columns -- rotates two thirds of its columns: with
+// the map above 21 of the 32 column tiles at N = 9216 are all q / k and 10 all v, and a launch ends with its slowest tile.
+// A wave column's 9 sub-tiles: 0-2 q and 3-5 k, pair groups u' = 3 wn + {0, 1, 2} (d = 8 u' .. 8 u' + 7 in slots 0..7, d + 48
+// in slots 8..15, as above), 6-8 the 48 plain v columns wn 48 .. of the head.  Sub-tiles i and i + 3 share their cos / sin quad.
+__host__ __device__ inline bool rope_grouped_ok(int64_t N, int64_t rope_cols, int head_dim) {
+    return head_dim == 96 && N > 0 && N % 288 == 0 && 3 * rope_cols == 2 * N;
+}
+// output column (= W row) behind slot `slot` (0..287) of tile `tile`; every aligned 8 slots are 8 consecutive columns
+__host__ __device__ inline int rope_grouped_col(int rope_cols, int tile, int slot) {
+    const int wn = slot >= 144, r = slot - wn * 144, i = r >> 4, w = r & 15;
+    if (i >= 6) return rope_cols + tile * 96 + wn * 48 + (i - 6) * 16 + w;
+    const int kind = i >= 3, up = 3 * wn + i - 3 * kind;
+    return kind * (rope_cols >> 1) + tile * 96 + up * 8 + (w & 7) + ((w & 8) ? 48 : 0);
 }
 
 // Tile order of both kernels: XCD-aware remap of the workgroup id (bijective), then grouped along m, so that workgroups
@@ -580,7 +609,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmArgs g) {
                         auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(own), __float_as_uint(own), false, false);
                         const float other = __uint_as_float(upper ? sw2[0] : sw2[1]);
                         // lower half: a*cos - b*sin; upper half: b*cos + a*sin  (rotate_half(x) = [-x2 | x1])
-                        o[t] = f2bf(upper ? own * cs[t] + other * sn[t] : own * cs[t] - other * sn[t]);
+                        o[t] = f2bf(rope_rotate(own, other, cs[t], sn[t], upper));
                     }
                 } else {
 #pragma unroll
@@ -866,7 +895,9 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs g) {
         {
             const int pw = min(max(lane - 8, 0), NI - 1);
             const int sl8 = (wave * NI + pw) * 8;
-            const int wrow = ROPE ? rope_col_of_slot(n0 + sl8, g.rope_cols, g.head_dim) : sl8;
+            const int wrow = !ROPE ? sl8
+                             : g.rope_grouped ? rope_grouped_col(g.rope_cols, tn, sl8)
+                                              : rope_col_of_slot(n0 + sl8, g.rope_cols, g.head_dim);
             tab = lane < 8 ? (uint32_t)((wave * 8 + lane) * 8 * (int)g.lda) * 2u : (uint32_t)(wrow * (int)g.ldw) * 2u;
         }
         const uint32_t va = (uint32_t)(srow * (int)g.lda + schunk * 8) * 2u, vw = (uint32_t)(srow * (int)g.ldw + schunk * 8) * 2u;
@@ -984,7 +1015,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs g) {
                         const float own = bf2f(f2bf(v[t]));
                         auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(own), __float_as_uint(own), false, false);
                         const float other = __uint_as_float(upper ? sw2[0] : sw2[1]);
-                        const float r_ = upper ? own * cs[t] + other * sn[t] : own * cs[t] - other * sn[t];
+                        const float r_ = rope_rotate(own, other, cs[t], sn[t], upper);
                         o[t] = rot ? r_ : v[t];
                     }
                     const uint32_t off = (m_ok && gs0 + en < g.N) ? (uint32_t)(ml * (int)g.ldc + n) * 2u : OOB;
@@ -992,8 +1023,69 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs g) {
                 });
             });
         };
-        if (g.nrm_rstd != nullptr) rope_store(std::true_type{});
-        else rope_store(std::false_type{});
+        // Head-grouped tile (rope_grouped_col; whole tiles: NI == 9 takes no others): which sub-tiles rotate is a compile-time
+        // property -- 0-2 (q) and 3-5 (k) rotate, i and i + 3 with the same cos / sin quad of pair group 3 wn + i % 3, so a row
+        // of sub-tiles reads 6 quads instead of 18; 6-8 (v) only scale, round and store: no table read, no swap, no select.
+        // Arithmetic per rotated element is rope_store's.
+        auto rope_store_grouped = [&](auto normc) {
+            constexpr bool NORM = decltype(normc)::value;
+            const int d0 = wn * 24 + (en & 7);
+            const int nq = tn * 96 + d0 + ((en & 8) ? 48 : 0);        // column of this lane's quad in sub-tile 0 (q)
+            const int nk_ = nq + (g.rope_cols >> 1);                   // ... in sub-tile 3 (k)
+            const int nv = g.rope_cols + tn * 96 + wn * 48 + en;       // ... in sub-tile 6 (v)
+            static_for<0, MI>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                const int ml = wm * 128 + j * 16 + em;
+                [[maybe_unused]] const float rs = NORM ? rs_lds[ml] : 1.0f;
+                const int row = ml * (int)g.ldc;
+                f32x4 cs3[3], sn3[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    cs3[c] = *reinterpret_cast<const f32x4*>(smem + (ml * 48 + d0 + c * 8) * 4);
+                    sn3[c] = *reinterpret_cast<const f32x4*>(smem + tab_bytes + (ml * 48 + d0 + c * 8) * 4);
+                }
+                static_for<0, 6>([&](auto ic) {
+                    constexpr int i = decltype(ic)::value, c = i % 3;
+                    f32x4 v = acc_of(ic, jc);
+                    if constexpr (NORM) {
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) v[t] *= rs;
+                    }
+                    const f32x4 cs = cs3[c], sn = sn3[c];
+                    f32x4 o;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const float own = bf2f(f2bf(v[t]));
+                        auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(own), __float_as_uint(own), false, false);
+                        const float other = __uint_as_float(upper ? sw2[0] : sw2[1]);
+                        o[t] = rope_rotate(own, other, cs[t], sn[t], upper);
+                    }
+                    const int n = (i < 3 ? nq : nk_) + c * 8;
+                    __builtin_amdgcn_raw_buffer_store_b64(pack4(o), rsC, (uint32_t)(row + n) * 2u, 0, 0);
+                });
+                static_for<6, NI>([&](auto ic) {
+                    constexpr int i = decltype(ic)::value;
+                    f32x4 v = acc_of(ic, jc);
+                    if constexpr (NORM) {
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) v[t] *= rs;
+                    }
+                    __builtin_amdgcn_raw_buffer_store_b64(pack4(v), rsC, (uint32_t)(row + nv + (i - 6) * 16) * 2u, 0, 0);
+                });
+            });
+        };
+        bool grouped = false;
+        if constexpr (NI == 9) {
+            grouped = g.rope_grouped != 0;
+            if (grouped) {
+                if (g.nrm_rstd != nullptr) rope_store_grouped(std::true_type{});
+                else rope_store_grouped(std::false_type{});
+            }
+        }
+        if (!grouped) {
+            if (g.nrm_rstd != nullptr) rope_store(std::true_type{});
+            else rope_store(std::false_type{});
+        }
     } else if constexpr (MODE == MODE_PLAIN) {
         auto plain_store = [&](auto epic, auto widec) {
             constexpr int EPI = decltype(epic)::value;
@@ -1385,6 +1477,10 @@ bool w4_ok(const GemmArgs& g, int64_t n_out) {
     return true;
 }
 
+// MODE_ROPE on 256 x 288 tiles: does the head-grouped slot map apply (rope_grouped_col: q, k and v with equally many 96-wide
+// heads)?  Every other shape keeps rope_col_of_slot and the epilogue that goes with it; the eight-wave kernels never look.
+bool w4_rope_grouped(const GemmArgs& g) { return rope_grouped_ok(g.N, g.rope_cols, g.head_dim); }
+
 // 256- or 192-wide tiles.  Cost of a round of 256 workgroups in units of one k-tile of a 256 x 256 round, fitted to in-step
 // kernel times of round 4 (o_proj 67 us and down_proj 152 us: one round of 192-wide tiles at 48 / 128 k-tiles; gate_up 292 us:
 // four rounds of 256-wide tiles at 48): a 256-wide k-tile 1.19 us, a 192-wide one 1.06 us (0.89 -- the loop is paced by the
@@ -1525,6 +1621,14 @@ VGPT_EXPORT int vgpt_gemm_last_launches(int32_t* out, int cap) {
         out[i * 6 + 3] = r.wtr; out[i * 6 + 4] = r.row0; out[i * 6 + 5] = r.rows;
     }
     return g_n_launch_recs;
+}
+
+// The head-grouped slot map of the 288-wide RoPE tile, through the function the kernel itself uses: output column behind slot
+// `slot` of column tile `tile`, -1 where the map does not apply (or tile / slot lie outside the matrix / the tile)
+VGPT_EXPORT int64_t vgpt_gemm_rope_grouped_col(int64_t N, int64_t rope_cols, int head_dim, int64_t tile, int slot) {
+    if (N >= (1 << 30) || !rope_grouped_ok(N, rope_cols, head_dim)) return -1;
+    if (tile < 0 || tile >= N / 288 || slot < 0 || slot >= 288) return -1;
+    return rope_grouped_col((int)rope_cols, (int)tile, slot);
 }
 
 /* ---- RMSNorm folded into the GEMMs around it ---- */
@@ -1725,6 +1829,7 @@ static int gemm_rope_impl(const void* A, const void* W, void* C, const float* co
     g.epi = VGPT_EPI_NONE; g.act = VGPT_ACT_NONE; g.I = 0;
     g.tiles_m = g.tiles_n = 0;
     g.rope_cos = cos_t; g.rope_sin = sin_t; g.rope_cols = n_rot_heads * head_dim; g.head_dim = head_dim;
+    g.rope_grouped = w4_rope_grouped(g);
     g.nrm_rstd = nrm_rstd;
     return launch<MODE_ROPE>(g, N, (hipStream_t)stream, "vgpt_gemm_bf16_rope");
 }
