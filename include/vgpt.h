@@ -409,6 +409,21 @@ int vgpt_sp_pack_qkv(const void* qkv, void* out, int64_t rows, int n_heads, int 
  * out (rows, n_ranks * block_width): out[t, i*block_width + c] = blocks[i, t, c] -- the heads of rank i land at their
  * place in head order, the o_proj operand of an unsharded step.  block_width % 8 == 0, 16-byte aligned pointers. */
 int vgpt_sp_unpack_ctx(const void* blocks, void* out, int64_t rows, int64_t block_width, int n_ranks, void* stream);
+/* The same two exchanges run backwards in the sharded training step (train.Stage1Trainer, sequence_parallel=True): the
+ * inverses of the two re-layouts above.
+ * vgpt_sp_pack_ctx: blocks[i, t, c] = ctx[t, i*block_width + c] -- ctx (rows, n_ranks * block_width) bf16, blocks
+ * (n_ranks, rows, block_width): d(ctx) of this rank's rows, cut by the rank that owns the heads.  Checks as
+ * vgpt_sp_unpack_ctx. */
+int vgpt_sp_pack_ctx(const void* ctx, void* blocks, int64_t rows, int64_t block_width, int n_ranks, void* stream);
+/* Inverse of vgpt_sp_pack_qkv: chunks (n_ranks, rows, (n_heads + 2 n_kv_heads) / n_ranks * head_dim) bf16 -> qkv
+ * (rows, (n_heads + 2 n_kv_heads) head_dim) laid out [q heads | k heads | v heads].  cos_t == sin_t == NULL: bytes only.
+ * With tables (rows, head_dim/2) fp32 the q and k heads are also rotated on the way through, bit for bit what
+ * vgpt_rope_qk_inplace would do to the unpacked rows (same bf16 inputs, fp32 arithmetic, one rounding); the v columns
+ * stay bytes.  The trainer passes cos and -sin: the inverse rotation of d(qkv).  Exactly one table NULL, null buffers,
+ * bad shapes, heads not multiples of n_ranks: VGPT_ERR_INVALID.  head_dim % 8 != 0 (with tables: head_dim/2 % 8 != 0),
+ * pointers (tables included) not 16-byte aligned, 2^31 vectors or more: VGPT_ERR_UNSUPPORTED.  rows == 0 is a no-op. */
+int vgpt_sp_unpack_qkv_rope(const void* chunks, void* qkv, const float* cos_t, const float* sin_t, int64_t rows,
+                            int n_heads, int n_kv_heads, int head_dim, int n_ranks, void* stream);
 
 /* z_model = bf16(z) */
 int vgpt_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);

@@ -85,6 +85,8 @@ SIGNATURES = {
     "vgpt_cast_f32_to_bf16": (c_int, [_P, _P, _I64, _P]),
     "vgpt_sp_pack_qkv": (c_int, [_P, _P, _I64, c_int, c_int, c_int, c_int, _P]),
     "vgpt_sp_unpack_ctx": (c_int, [_P, _P, _I64, _I64, c_int, _P]),
+    "vgpt_sp_pack_ctx": (c_int, [_P, _P, _I64, _I64, c_int, _P]),
+    "vgpt_sp_unpack_qkv_rope": (c_int, [_P, _P, _P, _P, _I64, c_int, c_int, c_int, c_int, _P]),
     "vgpt_groupnorm_stats": (c_int, [_P, _P, _I64, c_int, c_int, c_int, c_float, _P]),
     "vgpt_conv2d_fwd": (c_int, [_P] * 8 + [c_int] * 11 + [_I64, _I64, _P]),
     "vgpt_conv_bx3_packed_bytes": (c_int64, [c_int, c_int]),

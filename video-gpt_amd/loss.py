@@ -11,7 +11,10 @@ backward kernels of `train.Stage1Trainer`.  So
     {"loss": (frames,)} computed by the HIP forward (evaluation, logging); pass a `Stage1Trainer` as `model` and the
     same call also runs the backward, clipping and AdamW step (`update=True`), which is how a loop written against the
     reference's API trains here.
-At sequence-parallel size 1 the reference's `broadcast_data` calls (:150,168-172) are identities and are not issued.
+The reference's `broadcast_data` calls (:150,168-172) give every rank of a sequence-parallel group rank 0's x1 and
+draws.  Here: through a trainer that shares its rows (Stage1Trainer(sequence_parallel=True) under a group of P > 1) every
+rank draws (the RNG streams advance as in the reference) and the draws of the group's rank 0 are broadcast to the group;
+the batch itself travels by `sequence_parallel.broadcast_batch`.  At size 1 they are identities and are not issued.
 """
 from __future__ import annotations
 
@@ -105,6 +108,12 @@ def training_losses_x1_noise_input(model, x1, model_kwargs=None, snr_type="unifo
     clean = list(model_kwargs.get("input_img_latents") or [])
     x0, t, x0_in, t_in = draw_training_noise(x1, clean, input_noise, frame_blocks, exp_time)
     trainer = model if isinstance(model, Stage1Trainer) else Stage1Trainer.for_evaluation(model)
+    sp = getattr(trainer, "_sp", None)
+    if sp is not None:           # loss.py:150,168-172: the group trains on its rank 0's noise
+        import torch.distributed as dist
+        from . import sequence_parallel as SPM
+        x0, t, x0_in, t_in = SPM.broadcast_batch((x0, t, x0_in, t_in), dist.get_global_rank(sp["group"], 0), sp["group"],
+                                                   device=t.device)
     batch = {k: model_kwargs[k] for k in ("input_ids", "attention_mask", "position_ids", "input_image_sizes",
                                           "denoise_image_sizes", "time_emb_inx")}
     cat = lambda xs: torch.cat(list(xs), dim=0) if len(xs) > 0 else None

@@ -708,4 +708,7 @@ class LVMTraining(LVM):
                                         return_past_key_values, offload_model, vae, input_output_return)
 
 
-LVMTraining_CP = LVMTraining
+class LVMTraining_CP(LVMTraining):
+    """LVM/model.py:846-1107: the training model of the stage 2-4 scripts, whose forward gives every rank of the
+    sequence-parallel group an L/P slice of the sequence.  Same modules and same forward as LVMTraining; the sharded
+    training step lives where the backward lives, in train.Stage1Trainer(sequence_parallel=True)."""

@@ -775,6 +775,63 @@ def sp_unpack_ctx(blocks: torch.Tensor, n_ranks: int, out: Optional[torch.Tensor
     return out
 
 
+def sp_pack_ctx(ctx: torch.Tensor, n_ranks: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Inverse of sp_unpack_ctx (include/vgpt.h vgpt_sp_pack_ctx): (rows, n_ranks * Dc) -> (n_ranks, rows, Dc), block i =
+    the columns of rank i's heads.  The sharded trainer's d(ctx) on its way to the ranks that own the heads."""
+    _chk(ctx, BF16, "sp_pack_ctx.ctx")
+    if n_ranks < 1 or ctx.dim() != 2 or ctx.shape[-1] % n_ranks:
+        raise VgptError(f"sp_pack_ctx: ctx {tuple(ctx.shape)} is not (rows, {n_ranks} * block_width)")
+    rows, Dc = ctx.shape[0], ctx.shape[1] // n_ranks
+    if Dc % 8:
+        raise VgptError(f"sp_pack_ctx: block width {Dc} must be a multiple of 8")
+    shape = (n_ranks, rows, Dc)
+    if out is None:
+        out = torch.empty(*shape, dtype=BF16, device=ctx.device)
+    else:
+        _chk(out, BF16, "sp_pack_ctx.out")
+        if tuple(out.shape) != shape:
+            raise VgptError(f"sp_pack_ctx: out is {tuple(out.shape)}, needs {shape}")
+    if rows == 0:            # nothing to move (an empty tensor has no storage to point at)
+        return out
+    call("vgpt_sp_pack_ctx", ctx.data_ptr(), out.data_ptr(), rows, Dc, n_ranks, _stream())
+    return out
+
+
+def sp_unpack_qkv_rope(chunks: torch.Tensor, n_ranks: int, n_heads: int, n_kv_heads: int, head_dim: int,
+                       cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Inverse of sp_pack_qkv (include/vgpt.h vgpt_sp_unpack_qkv_rope): (n_ranks, rows, (n_heads + 2 n_kv_heads) / n_ranks *
+    head_dim) -> (rows, (n_heads + 2 n_kv_heads) head_dim) as [q heads | k heads | v heads].  With cos / sin (rows,
+    head_dim/2) fp32 the q and k heads are rotated on the way through: bit for bit rope_qk_inplace on the unpacked rows."""
+    _chk(chunks, BF16, "sp_unpack_qkv_rope.chunks")
+    if n_ranks < 1 or n_heads % n_ranks or n_kv_heads % n_ranks:
+        raise VgptError(f"sp_unpack_qkv_rope: n_heads {n_heads} and n_kv_heads {n_kv_heads} must be multiples of n_ranks "
+                        f"{n_ranks}")
+    W = (n_heads + 2 * n_kv_heads) * head_dim
+    if head_dim % 8 or chunks.dim() != 3 or chunks.shape[0] != n_ranks or chunks.shape[-1] != W // n_ranks:
+        raise VgptError(f"sp_unpack_qkv_rope: chunks {tuple(chunks.shape)} are not ({n_ranks}, rows, {W // n_ranks}) "
+                        "(head_dim a multiple of 8)")
+    rows = chunks.shape[1]
+    if (cos is None) != (sin is None):
+        raise VgptError("sp_unpack_qkv_rope: cos and sin come together or not at all")
+    if cos is not None:
+        _chk(cos, torch.float32, "sp_unpack_qkv_rope.cos"); _chk(sin, torch.float32, "sp_unpack_qkv_rope.sin")
+        if head_dim % 16 or tuple(cos.shape) != (rows, head_dim // 2) or tuple(sin.shape) != (rows, head_dim // 2):
+            raise VgptError(f"sp_unpack_qkv_rope: tables {tuple(cos.shape)} / {tuple(sin.shape)} are not ({rows}, "
+                            f"{head_dim // 2}) (head_dim / 2 a multiple of 8)")
+    if out is None:
+        out = torch.empty(rows, W, dtype=BF16, device=chunks.device)
+    else:
+        _chk(out, BF16, "sp_unpack_qkv_rope.out")
+        if out.shape[-1] != W or out.numel() != rows * W:
+            raise VgptError(f"sp_unpack_qkv_rope: out {tuple(out.shape)} is not ({rows}, {W})")
+    if rows == 0:
+        return out
+    call("vgpt_sp_unpack_qkv_rope", chunks.data_ptr(), out.data_ptr(), _ptr(cos), _ptr(sin), rows, n_heads, n_kv_heads,
+         head_dim, n_ranks, _stream())
+    return out
+
+
 # ---- sampler ----------------------------------------------------------------------------------
 
 def sampler_set_timesteps(sigma: torch.Tensor, step: torch.Tensor, timesteps: torch.Tensor):

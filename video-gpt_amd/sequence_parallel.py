@@ -130,6 +130,28 @@ def gather_sequence(hidden: torch.Tensor, group=None) -> torch.Tensor:
     return torch.cat(parts, dim=1)
 
 
+def broadcast_batch(obj, src: int, group=None, device=None):
+    """`broadcast_data` of the reference's sequence-parallel scripts (train_x1_stage2_noiseinput_frameblock.py:370-373,
+    LVM/train_helper/loss.py:150,168-172): every rank of `group` returns rank `src`'s `obj` (`src` is a GLOBAL rank, as in
+    torch.distributed.broadcast) -- any nesting of dicts, lists, tuples, tensors and plain values.  Tensors travel through
+    host memory and come back on `device` (default: the CPU).  Host side, once per batch: not on the step's hot path."""
+    group = group if group is not None else _GROUP
+    if group is None or dist.get_world_size(group) == 1:
+        return obj
+
+    def walk(o, fn):
+        if torch.is_tensor(o):
+            return fn(o)
+        if isinstance(o, dict):
+            return {k: walk(v, fn) for k, v in o.items()}
+        if isinstance(o, (list, tuple)):
+            return type(o)(walk(v, fn) for v in o)
+        return o
+    box = [walk(obj, lambda t: t.detach().cpu()) if dist.get_rank() == src else None]
+    dist.broadcast_object_list(box, src=src, group=group)
+    return box[0] if device is None else walk(box[0], lambda t: t.to(device))
+
+
 # ---- flat exchanges: the sharded sampler engine (engine.StaticDenoiser with sequence_parallel=True) and the trainer's
 #      sharded optimizer (train.Stage1Trainer with dp_sharding="optimizer") ----
 

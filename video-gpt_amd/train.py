@@ -23,7 +23,12 @@ optimizer to DeepSpeed's bf16 AdamW (fp32 master weights).  Here:
   * gradient_accumulation_steps=A keeps one fp32 accumulator per gradient bucket and adds every micro-step's bucket to it
     right where the bucket would be exchanged; the last micro-step writes the once-rounded sum back into the bucket and the
     exchange, clip and AdamW run on it unchanged, 1/A folded in where 1/world is.  use_ema=True keeps an fp32 EMA of the
-    fp32 master weights, moved inside the AdamW launch (vgpt_adamw_ema_step); DESIGN.md §6b.
+    fp32 master weights, moved inside the AdamW launch (vgpt_adamw_ema_step); DESIGN.md §6b;
+  * sequence_parallel=True under a group of P > 1 ranks (LVMTraining_CP, --sequence_parallel_size; LVM/model.py:1101-1107,
+    LVM/transform/sdpa_transform.py:94-159, LVM/utils.py:148-174) shares the rows of ONE packed clip between the P ranks:
+    the row-local work of forward and backward runs on this rank's share, attention and its backward on this rank's heads
+    over all rows, with two exchanges per layer each way; every saved activation is 1/P of the unsharded step's and the
+    gradient buckets hold partial sums over the share that the data-parallel exchange adds up.
 """
 from __future__ import annotations
 
@@ -40,7 +45,7 @@ from . import ops
 from . import ops_lora as LO
 from . import ops_train as T
 from . import sequence_parallel as SPM
-from .engine import _rows, bump_weight_generation, count_left_pads, pack_left_padded
+from .engine import _rows, bump_weight_generation, count_left_pads, pack_left_padded, sp_shares
 from .ops import BF16, VgptError
 
 F32 = torch.float32
@@ -48,6 +53,9 @@ DP_SHARDING_MODES = ("none", "optimizer")
 LR_SCHEDULERS = ("constant", "constant_with_warmup", "linear", "cosine", "cosine_with_restarts", "polynomial")
 LR_END = 1e-7           # end LR of "polynomial" (get_scheduler passes none: the schedule's own default)
 LORA_TARGETS = ("qkv_proj", "o_proj")
+# gradients a sequence-parallel rank computes on replicated rows (the heads behind the gathered final norm): identical on
+# every rank of the group, so they enter the data-parallel sum from SP rank 0 only
+SP_REPLICATED = ("final_layer.", "t_embedder.", "input_final_layer.")
 
 
 def lora_key(layer: int, module: str, ab: str) -> str:
@@ -142,7 +150,7 @@ class Stage1Trainer:
                  lora_alpha: Optional[float] = None, lora_target_modules=LORA_TARGETS,
                  gradient_accumulation_steps: int = 1, use_ema: bool = False, ema_decay: float = 0.9999,
                  lr_num_training_steps: Optional[int] = None, lr_num_cycles: Optional[float] = None,
-                 lr_power: float = 1.0):
+                 lr_power: float = 1.0, sequence_parallel: bool = False, sp_group=None, check_sp_inputs: bool = True):
         """lr_scheduler / lr_warmup_steps / lr_num_training_steps / lr_num_cycles / lr_power: diffusers' get_scheduler
         (train_x1_stage1_noiseinput.py:279-283, 513-521; the scripts use constant_with_warmup), one of LR_SCHEDULERS: the
         k-th optimizer step (k = 0, 1, ...) runs at lr * lr_factor(name, k * lr_scheduler_steps_per_optimizer_step, ...);
@@ -184,7 +192,15 @@ class Stage1Trainer:
         reference's update_ema(ema, model, decay=0)), moved inside every AdamW launch: ema = d ema + (1 - d) master_new.
         Deliberate difference: the reference's EMA is a deepcopy of the model in the model's dtype, and under bf16
         parameters an increment of relative size 1 - 0.9999 lies below bf16 resolution, so that EMA barely moves; here the
-        EMA is fp32 and follows the fp32 master.  Full fine-tuning only.  ema_state_dict() / ema_weights() read it."""
+        EMA is fp32 and follows the fp32 master.  Full fine-tuning only.  ema_state_dict() / ema_weights() read it.
+        sequence_parallel / sp_group (--sequence_parallel_size with LVMTraining_CP): Ulysses sequence parallelism through
+        forward and backward over `sp_group` (default: sequence_parallel.get_sequence_parallel_group()); on when the flag
+        is set and the group has P > 1 ranks, which then must all call step() with the SAME batch, latents and noise
+        (sequence_parallel.broadcast_batch; loss.training_losses_x1_noise_input broadcasts its draws).  The world is
+        world / P data-parallel replicas of P ranks; the update equals the P = 1 update on the same clips up to summation
+        order (unlike the reference, whose decoder gradients come out scaled 1 / P).  check_sp_inputs:
+        every sharded step() first all-gathers a 16-byte digest of (input_ids, t, x1.shape) over the group and raises on
+        every rank when they differ; False skips that collective."""
         model._check_ready()
         if hasattr(model, "release_engines"):
             model.release_engines()          # a sampler engine cached on the model holds GBs the trainer's buffers want
@@ -228,6 +244,8 @@ class Stage1Trainer:
         self.dev = model.llm.norm.weight.device
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.rank = dist.get_rank() if self.world > 1 else 0
+        self._sp = self._sp_state(sequence_parallel, sp_group, lora_rank)     # refusals before any collective
+        self.check_sp_inputs = bool(check_sp_inputs)
         if lora_rank is not None:
             if isinstance(lora_rank, bool) or int(lora_rank) != lora_rank or not 1 <= int(lora_rank) <= 64:
                 raise VgptError(f"lora_rank {lora_rank!r}: an integer rank 1 <= r <= 64 is built")
@@ -332,6 +350,48 @@ class Stage1Trainer:
         bump_weight_generation(model)     # storage re-pointed; from here on the optimizer writes it through raw pointers
         self._init_scalars()
         self._init_ema()
+
+    # ---- sequence parallelism ------------------------------------------------------------------------------------------
+    def _sp_state(self, flag, group, lora_rank):
+        """None (off), or {"group", "P", "r"} of the sequence-parallel group this trainer shares its rows with.  Every
+        refusal depends on arguments and group sizes alone, so all ranks raise together and no collective is issued."""
+        if not flag:
+            return None
+        if group is None:
+            group = SPM.get_sequence_parallel_group()
+        if group is None:
+            raise VgptError("sequence_parallel=True needs a group: pass sp_group or call "
+                            "sequence_parallel.initialize_sequence_parallel_state() first")
+        P = dist.get_world_size(group)
+        if P < 1:
+            raise VgptError("sequence_parallel: this rank is not a member of sp_group")
+        if P == 1:
+            return None
+        if lora_rank is not None:
+            raise VgptError("lora_rank with sequence_parallel: adapters under sequence parallelism are not built")
+        if self.world % P:
+            raise VgptError(f"sequence_parallel: the world size {self.world} is not a multiple of the group size {P}")
+        nq, nk = self.cfg.num_attention_heads, self.cfg.num_key_value_heads
+        if nq % P or nk % P:
+            raise VgptError(f"sequence_parallel over {P} ranks needs num_attention_heads ({nq}) and num_key_value_heads "
+                            f"({nk}) divisible by {P}")
+        return {"group": group, "P": P, "r": dist.get_rank(group)}
+
+    def _check_sp_batch(self, batch, x1, t):
+        """All ranks of the group must train on the same clip and the same noise: one small collective, and every rank
+        raises when the digests differ (nobody is left waiting in an exchange)."""
+        import hashlib
+        h = hashlib.blake2b(digest_size=16)
+        h.update(batch["input_ids"].detach().cpu().contiguous().numpy().tobytes())
+        h.update(t.detach().to("cpu", F32).contiguous().numpy().tobytes())
+        h.update(repr(tuple(x1.shape)).encode())
+        mine = torch.frombuffer(bytearray(h.digest()), dtype=torch.uint8).to(self.dev)
+        every = SPM.all_gather_flat(mine, self._sp["group"]).cpu()
+        if not bool((every == every[0]).all()):
+            bad = [i for i in range(every.shape[0]) if not torch.equal(every[i], every[0])]
+            raise VgptError(f"Stage1Trainer.step: the ranks of the sequence-parallel group were given different inputs "
+                            f"(input_ids, t or x1.shape of group ranks {bad} differ from group rank 0's): broadcast the "
+                            "batch and the noise inside the group (sequence_parallel.broadcast_batch)")
 
     # ---- LoRA mode --------------------------------------------------------------------------------------------------
     def _init_lora(self, r: int, alpha, targets):
@@ -557,7 +617,9 @@ class Stage1Trainer:
         B, L = ids.shape
         row_of = lambda b, s: b * L + s
         pads = count_left_pads(mask) if self.pack_padding else []
-        if any(pads):
+        if self._sp is not None and B > 1 and not any(pads):
+            pads = [0] * B               # the shares cut ONE sequence: rows of a batch are laid end to end
+        if any(pads) or (self._sp is not None and B > 1):
             ids, pos, mask, offs = pack_left_padded(ids, pos, mask, pads)
             row_of = lambda b, s: offs[b] + s - pads[b]
             B, L = ids.shape
@@ -587,6 +649,9 @@ class Stage1Trainer:
         if update:
             self._refuse_inside_ema_weights("step(update=True)")
         m, cfg = self.model, self.cfg
+        sp = self._sp
+        if sp is not None and self.check_sp_inputs:
+            self._check_sp_batch(batch, x1, t)
         prep = self._prepare(batch)
         # the previous step's update may still be running on its own stream, its all-gathers (sharded) still in flight
         self._await_params(-1)               # embeddings, heads, final norm: read from the start
@@ -604,8 +669,19 @@ class Stage1Trainer:
         if clean is not None and clean.shape[0] > 0:
             cl = T.lerp_frames(clean.to(self.dev, F32).contiguous(), x0_in.to(self.dev, F32).contiguous(),
                                t_in.to(self.dev, F32).contiguous(), self._buf("cl", tuple(clean.shape)))
-        hbuf = self._buf("h", (nl + 1, M, H))          # layer inputs (h[l]) and the last output
-        seq = hbuf[0]
+        # sequence parallelism: this rank runs rows [r0, r1) of the one packed sequence (Ms of the M rows) through the
+        # row-local work and its nq / P heads (Wl fused q|k|v columns, dc context columns) through attention over all rows
+        Ms, rope = M, prep["rope"]
+        if sp is not None:
+            P = sp["P"]
+            shares, _ = sp_shares(M, P)
+            sizes = [e_ - a_ for a_, e_ in shares]
+            r0, r1 = shares[sp["r"]]
+            Ms, Wl, dc = r1 - r0, (nq + 2 * nk) // P * hd, nq // P * hd
+            rope = tuple(t_.view(-1, hd // 2)[r0:r1] for t_ in prep["rope"])
+        hbuf = self._buf("h", (nl + 1, Ms, H))         # layer inputs (h[l]) and the last output
+        # the sequence assembly is cheap and runs on all rows on every rank; the share is a copy of its rows
+        seq = hbuf[0] if sp is None else self._buf("seq_all", (M, H))
         ops.embed_gather(prep["ids"], m.llm.embed_tokens.weight, out=seq.view(B, L, H))
         pos = m.pos_embed[0]
         if cl is not None:
@@ -618,13 +694,26 @@ class Stage1Trainer:
         ops.linear_small(tt_act, tt[2].weight, tt[2].bias, out=seq, out_row=prep["t_rows"], ldo=H)
         ops.patch_embed(xt, m.x_embedder.proj.weight, m.x_embedder.proj.bias, pos, prep["x_rows"], seq,
                         m.pos_embed_max_size)
+        if sp is not None:
+            hbuf[0].copy_(seq[r0:r1])
         # saved activations: every layer's (normal) or ONE layer's worth, recomputed per layer in the backward (checkpointing)
         ck = self.gradient_checkpointing
         ns = 1 if ck else nl
-        n1 = self._buf("n1", (ns, M, H)); qkv = self._buf("qkv", (ns, M, (nq + 2 * nk) * hd))
-        ctx = self._buf("ctx", (ns, M, nq * hd)); h2 = self._buf("h2", (ns, M, H)); n2 = self._buf("n2", (ns, M, H))
-        gu = self._buf("gu", (ns, M, 2 * I)); act = self._buf("act", (ns, M, I))
-        lse = self._buf("lse", (ns, B, nq, L), F32)
+        n1 = self._buf("n1", (ns, Ms, H))
+        ctx = self._buf("ctx", (ns, Ms, nq * hd)); h2 = self._buf("h2", (ns, Ms, H)); n2 = self._buf("n2", (ns, Ms, H))
+        gu = self._buf("gu", (ns, Ms, 2 * I)); act = self._buf("act", (ns, Ms, I))
+        if sp is None:
+            qkv = self._buf("qkv", (ns, M, (nq + 2 * nk) * hd))
+            lse = self._buf("lse", (ns, B, nq, L), F32)
+        else:
+            # kept per layer: the fused q|k|v rows of EVERY rank for this rank's heads, their context and lse; the share's
+            # own q|k|v rows of all heads ("qkv") and the exchange buffers are transient
+            qkv = self._buf("qkv", (Ms, (nq + 2 * nk) * hd))
+            qkv_h = self._buf("qkv_heads", (ns, M, Wl)); ctx_h = self._buf("ctx_heads", (ns, M, dc))
+            lse = self._buf("lse", (ns, 1, nq // P, M), F32)
+            send = self._buf("sp_send", (P, Ms, Wl)); ctx_recv = self._buf("sp_ctx_recv", (P, Ms, dc))
+            by_sender = [[n * Wl] * P for n in sizes]                     # every rank sends its rows to every rank
+            by_owner = [[n * dc for n in sizes] for _ in range(P)]        # every rank sends each rank that rank's rows
         sv = lambda li: 0 if ck else li
         lora = self.lora_rank is not None
         lq, lo = lora and "qkv_proj" in self.lora_targets, lora and "o_proj" in self.lora_targets
@@ -642,9 +731,18 @@ class Stage1Trainer:
                 ops.linear(n1[k], at.qkv_proj.weight, out=qkv[k])
                 LO.lora_down(n1[k], aq["A"], rp, out=u_q[k])
                 LO.lora_up_add(qkv[k], u_q[k], aq["B"], alpha=ls, rope=(prep["rope"][0], prep["rope"][1], nq, nk, hd))
-            else:
+            elif sp is None:
                 ops.linear_qkv_rope(n1[k], at.qkv_proj.weight, prep["rope"][0], prep["rope"][1], nq, nk, hd, out=qkv[k])
-            T.attention_qkv_train(qkv[k].view(B, L, -1), prep["pm"], nq, nk, hd, ctx[k].view(B, L, -1), lse[k])
+            if sp is None:
+                T.attention_qkv_train(qkv[k].view(B, L, -1), prep["pm"], nq, nk, hd, ctx[k].view(B, L, -1), lse[k])
+            else:       # engine.StaticDenoiser._sp_attention with the training forward's kernel
+                ops.linear_qkv_rope(n1[k], at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=qkv)
+                ops.sp_pack_qkv(qkv, P, nq, nk, hd, out=send)
+                SPM.exchange_split(send, qkv_h[k], by_sender, sp["group"])
+                T.attention_qkv_train(qkv_h[k].view(1, M, Wl), prep["pm"], nq // P, nk // P, hd, ctx_h[k].view(1, M, dc),
+                                      lse[k])
+                SPM.exchange_split(ctx_h[k], ctx_recv, by_owner, sp["group"])
+                ops.sp_unpack_ctx(ctx_recv, P, out=ctx[k])
             ops.linear(ctx[k], at.o_proj.weight, residual=hbuf[li], out=h2[k])
             if lo:
                 ao = self._lora_w[(li, "o_proj")]
@@ -660,7 +758,18 @@ class Stage1Trainer:
 
         for li in range(nl):
             layer_forward(li)
-        nrm = ops.rmsnorm(hbuf[nl], m.llm.norm.weight, m.llm.norm.variance_epsilon, out=self._buf("nrm", (M, H)))
+        if sp is None:
+            nrm = ops.rmsnorm(hbuf[nl], m.llm.norm.weight, m.llm.norm.variance_epsilon, out=self._buf("nrm", (M, H)))
+        else:
+            # final norm on the share, then ONE exchange leaves the normed rows of every rank on every rank (Gather.forward,
+            # LVM/utils.py:148-161; shares padded to the largest): the heads below, the loss and their backward run
+            # replicated, so the loss vector is the same bits on every rank
+            pad = self._buf("nrm_pad", (max(sizes), H))
+            ops.rmsnorm(hbuf[nl], m.llm.norm.weight, m.llm.norm.variance_epsilon, out=pad[:Ms])
+            every = SPM.all_gather_flat(pad, sp["group"], out=self._buf("nrm_every", (P, max(sizes) * H)))
+            nrm = self._buf("nrm", (M, H))
+            for i, (a_, e_) in enumerate(shares):
+                nrm[a_:e_].copy_(every[i].view(-1, H)[:e_ - a_])
         te_pre = ops.linear_small(sin, te[0].weight, te[0].bias)
         te_act = T.act_fwd(te_pre, ops.ACT_SILU)
         temb = ops.linear_small(te_act, te[2].weight, te[2].bias)
@@ -720,8 +829,10 @@ class Stage1Trainer:
             T.matmul(dyin, vin, out=g["input_final_layer.weight"], ta=True)
             T.colsum(dyin, g["input_final_layer.bias"])
             dnrm.index_copy_(0, prep["c_idx"], T.matmul(dyin, head.weight))  # condition rows: no other gradient reaches them here
-        dh = self._buf("dh", (M, H)); dh_b = self._buf("dh_b", (M, H))
-        T.rmsnorm_bwd(hbuf[nl], m.llm.norm.weight, dnrm, dh, g["llm.norm.weight"], m.llm.norm.variance_epsilon)
+        dh = self._buf("dh", (Ms, H)); dh_b = self._buf("dh_b", (Ms, H))
+        # sharded: every rank keeps its own rows of dnrm (Gather.backward, LVM/utils.py:163-169): no exchange
+        T.rmsnorm_bwd(hbuf[nl], m.llm.norm.weight, dnrm if sp is None else dnrm[r0:r1], dh, g["llm.norm.weight"],
+                      m.llm.norm.variance_epsilon)
         # adaLN + t_embedder
         T.matmul(dmod, st, out=g["final_layer.adaLN_modulation.1.weight"], ta=True)
         T.colsum(dmod, g["final_layer.adaLN_modulation.1.bias"])
@@ -729,10 +840,18 @@ class Stage1Trainer:
         self._mlp_bwd("t_embedder", te, dtemb, te_act, te_pre, sin)
         # decoder layers, last to first
         sw = sa = sb = None   # dX / dW read their operands transposed inside the GEMM (vgpt_gemm_bf16_tr)
-        dact = self._buf("dact", (M, I)); dgu = self._buf("dgu", (M, 2 * I)); dn = self._buf("dn", (M, H))
-        dctx = self._buf("dctx", (M, nq * hd)); dqkv = self._buf("dqkv", (M, (nq + 2 * nk) * hd))
-        delta = self._buf("delta", (B, nq, L), F32)
+        dact = self._buf("dact", (Ms, I)); dgu = self._buf("dgu", (Ms, 2 * I)); dn = self._buf("dn", (Ms, H))
+        dctx = self._buf("dctx", (Ms, nq * hd)); dqkv = self._buf("dqkv", (Ms, (nq + 2 * nk) * hd))
         nsin = self._neg_sin(prep)
+        if sp is None:
+            delta = self._buf("delta", (B, nq, L), F32)
+        else:
+            delta = self._buf("delta", (1, nq // P, M), F32)
+            nsin = nsin.view(-1, hd // 2)[r0:r1]
+            dctx_send = self._buf("sp_dctx_send", (P, Ms, dc)); dctx_h = self._buf("dctx_heads", (M, dc))
+            dqkv_h = self._buf("dqkv_heads", (M, Wl)); dqkv_recv = self._buf("sp_dqkv_recv", (P, Ms, Wl))
+            ctx_by_sender = [[n * dc] * P for n in sizes]
+            qkv_by_owner = [[n * Wl for n in sizes] for _ in range(P)]
         handles = []
         for li in range(nl - 1, -1, -1):
             layer = m.llm.layers[li]
@@ -751,9 +870,19 @@ class Stage1Trainer:
                           layer.post_attention_layernorm.variance_epsilon, dres=dh)       # dh2
             T.linear_dw(dh_b, ctx[k], sa, sb, g[names[1]])                             # dW_o
             T.linear_dx(dh_b, at.o_proj.weight, sw, out=dctx)
-            T.attention_qkv_bwd(qkv[k].view(B, L, -1), ctx[k].view(B, L, -1), dctx.view(B, L, -1), lse[k], delta,
-                                dqkv.view(B, L, -1), prep["pm"], nq, nk, hd)
-            ops.rope_qk_inplace(dqkv, prep["rope"][0], nsin, nq, nk, hd)                 # inverse rotation
+            if sp is None:
+                T.attention_qkv_bwd(qkv[k].view(B, L, -1), ctx[k].view(B, L, -1), dctx.view(B, L, -1), lse[k], delta,
+                                    dqkv.view(B, L, -1), prep["pm"], nq, nk, hd)
+                ops.rope_qk_inplace(dqkv, prep["rope"][0], nsin, nq, nk, hd)             # inverse rotation
+            else:
+                # the forward's two exchanges, mirrored: d(ctx) of my rows goes to the ranks that own the heads, d(qkv) of
+                # my heads goes back to the ranks that own the rows, and is rotated back on its way into row order
+                ops.sp_pack_ctx(dctx, P, out=dctx_send)
+                SPM.exchange_split(dctx_send, dctx_h, ctx_by_sender, sp["group"])
+                T.attention_qkv_bwd(qkv_h[k].view(1, M, Wl), ctx_h[k].view(1, M, dc), dctx_h.view(1, M, dc), lse[k], delta,
+                                    dqkv_h.view(1, M, Wl), prep["pm"], nq // P, nk // P, hd)
+                SPM.exchange_split(dqkv_h, dqkv_recv, qkv_by_owner, sp["group"])
+                ops.sp_unpack_qkv_rope(dqkv_recv, P, nq, nk, hd, rope[0], nsin, out=dqkv)
             T.linear_dw(dqkv, n1[k], sa, sb, g[names[0]])                              # dW_qkv
             T.linear_dx(dqkv, at.qkv_proj.weight, sw, out=dn)
             T.rmsnorm_bwd(hbuf[li], layer.input_layernorm.weight, dn, dh,
@@ -763,8 +892,15 @@ class Stage1Trainer:
                 T.grad_accumulate(self._accumulators()[1][li], self.layer_buckets[li], acc_mode)
             if exchange and self.world > 1 and not self.skip_allreduce and self.overlap_allreduce:
                 handles.append(self._reduce(self.layer_buckets[li]))
-        # heads fed by dseq = dh
+        # heads fed by dseq = dh (sharded: zero outside the share, so what follows yields this rank's partial gradients)
         dseq = dh
+        if sp is not None:
+            dseq = self._buf("dseq", (M, H)); dseq.zero_()
+            dseq[r0:r1].copy_(dh)
+            if sp["r"] > 0:      # computed on replicated rows: they enter the sum over the ranks from SP rank 0 alone
+                for name in g:
+                    if name.startswith(SP_REPLICATED):
+                        g[name].zero_()
         dtt = T.gather_rows(dseq, prep["t_rows"], 1)
         self._mlp_bwd("time_token", tt, dtt, tt_act, tt_pre, sin)
         self._patch_bwd("x_embedder", T.gather_rows(dseq, prep["x_rows"], ntok), xt)
@@ -909,7 +1045,7 @@ class Stage1Trainer:
             # every rank's sum over its reduced shards, in rank order, added on the device in a fixed order by clip_coef:
             # every rank computes the same norm and coefficient
             partials = SPM.all_gather_flat(self.sumsq, self._group, out=self._partials).view(-1)
-        w = float(self.world * micro_batches)
+        w = float(self.world // (self._sp["P"] if self._sp else 1) * micro_batches)     # data-parallel replicas x micro-batches
         # norm of the AVERAGED gradient = norm(sum)/world; coefficient already carries the 1/world factor (and 1/A, when the
         # buckets hold the sum over A micro-batches)
         T.clip_coef(partials, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w)
