@@ -543,6 +543,35 @@ int vgpt_ln_mod_bwd(const void* dv, const float* xhat, const float* rstd, const 
 /* embed_tokens backward: dtable[ids[r]] += dseq[r] for rows with keep[r] != 0 (fp32 atomics). */
 int vgpt_embed_bwd(const int64_t* ids, const uint8_t* keep, const void* dseq, float* dtable, int64_t rows, int64_t H,
                    int64_t vocab, void* stream);
+/* Deterministic twins of the three entry points above that add with float atomics (Stage1Trainer(deterministic=True),
+ * DESIGN.md 6d).  Same arguments plus a workspace, no float atomics: every sum is cut into partials whose membership
+ * depends on the shape alone (for the embedding: on ids and keep), the partials are written with plain stores and ONE
+ * writer per output element adds them in ascending order on top of the caller's value.  Same inputs give the same bits on
+ * every launch.  ws must be 16-byte aligned and hold at least what the matching *_workspace_bytes query answers (-1 on a
+ * negative argument); its contents need no initialisation and are garbage afterwards.
+ *
+ * vgpt_rmsnorm_bwd_det: dx and rstd_ws are vgpt_rmsnorm_bwd's, bit for bit (the same row kernel).  dw: the twin's row
+ * strips (min(ceil(rows/4), 128) wanted, a function of rows alone) store their sums at ws[strip][H]; a second launch adds
+ * the strips 0, 1, ... per column and then dw[c] += total (the caller zeroes dw, or keeps a running sum in it). */
+int64_t vgpt_rmsnorm_bwd_det_workspace_bytes(int64_t rows, int64_t H);
+int vgpt_rmsnorm_bwd_det(const void* x, const void* w, const void* dy, const void* dres, void* dx, float* dw,
+                         float* rstd_ws /* rows floats */, int64_t rows, int64_t H, float eps, float* ws, int64_t ws_floats,
+                         void* stream);
+/* vgpt_ln_mod_bwd_det: dhidden is vgpt_ln_mod_bwd's, bit for bit.  A wave walks ceil(ntok / 64) tokens of one frame (at
+ * most 64 waves per frame, a function of ntok alone) and stores its dshift | dscale sums at ws[f][wave][2H]; a second
+ * launch adds the waves 0, 1, ... per frame and column and then dmod[f][c] += total. */
+int64_t vgpt_ln_mod_bwd_det_workspace_bytes(int64_t n_frames, int64_t ntok, int64_t H);
+int vgpt_ln_mod_bwd_det(const void* dv, const float* xhat, const float* rstd, const void* mod, const int32_t* dst_row,
+                        void* dhidden, float* dmod, int n_frames, int ntok, int64_t H, float* ws, int64_t ws_floats,
+                        void* stream);
+/* vgpt_embed_bwd_det (H % 8 == 0, vocab < 2^31): the kept, in-range rows are ranked by (id, row) with rows^2 integer
+ * comparisons; one workgroup per id that occurs and 256 columns adds that id's rows -- eight interleaved row slots, each
+ * in ascending row order, then the slots 0..7 -- and the one writer of dtable[id][c] adds the total to the caller's
+ * value.  The order depends on (ids, keep, rows, H) only.  Table rows whose id never occurs are neither read nor
+ * written.  ws: int32 words. */
+int64_t vgpt_embed_bwd_det_workspace_bytes(int64_t rows);
+int vgpt_embed_bwd_det(const int64_t* ids, const uint8_t* keep, const void* dseq, float* dtable, int64_t rows, int64_t H,
+                       int64_t vocab, int32_t* ws, int64_t ws_ints, void* stream);
 /* (n_frames, C, h, w) -> (n_frames*ntok, 16) patch vectors; gradient of unpatchify; row-segment gather. */
 int vgpt_patchify(const void* x, void* patches, int n_frames, int C, int h, int w, void* stream);
 int vgpt_unpatchify_bwd(const void* dpred, void* dy16, int n_frames, int C, int h, int w, void* stream);

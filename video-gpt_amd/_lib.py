@@ -119,6 +119,12 @@ SIGNATURES = {
     "vgpt_ln_mod_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _I64, c_float, _P]),
     "vgpt_ln_mod_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _I64, _P]),
     "vgpt_embed_bwd": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P]),
+    "vgpt_rmsnorm_bwd_det_workspace_bytes": (_I64, [_I64, _I64]),
+    "vgpt_rmsnorm_bwd_det": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, c_float, _P, _I64, _P]),
+    "vgpt_ln_mod_bwd_det_workspace_bytes": (_I64, [_I64, _I64, _I64]),
+    "vgpt_ln_mod_bwd_det": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _I64, _P, _I64, _P]),
+    "vgpt_embed_bwd_det_workspace_bytes": (_I64, [_I64]),
+    "vgpt_embed_bwd_det": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _I64, _P]),
     "vgpt_patchify": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "vgpt_unpatchify_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "vgpt_gather_rows": (c_int, [_P, _P, _P, c_int, c_int, _I64, _P]),

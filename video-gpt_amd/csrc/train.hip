@@ -453,6 +453,259 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const int64_t* __restric
     }
 }
 
+// ---- deterministic twins of the three reductions above (vgpt_*_det): no float atomics ----------------
+// Each sum is split into partials whose membership depends on the shape alone, the partials go to a workspace with
+// plain 16-byte stores, and one writer per output column adds them in ascending order on top of the caller's value.
+
+// rmsnorm dw, stage 1: rmsnorm_bwd_dw_kernel's strip walk; the strip's sum goes to part[strip][H] instead of an atomic.
+__global__ __launch_bounds__(512) void rmsnorm_bwd_dw_part_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
+                                                                  const float* __restrict__ rstd, float* __restrict__ part,
+                                                                  int64_t rows, int H, int rows_per_strip) {
+    __shared__ float red[3][128][9];
+    const int cg = threadIdx.x & 127, rl = threadIdx.x >> 7;
+    const int off = (blockIdx.x * 128 + cg) * 8;
+    const bool live = off < H;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_strip;
+    const int64_t r1 = r0 + rows_per_strip < rows ? r0 + rows_per_strip : rows;
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    if (live) {
+        int64_t r = r0 + rl;
+        for (; r + 12 < r1; r += 16) {
+            bf16x8 xb[4], db[4];
+            float rs[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                xb[u] = *reinterpret_cast<const bf16x8*>(x + (r + 4 * u) * H + off);
+                db[u] = *reinterpret_cast<const bf16x8*>(dy + (r + 4 * u) * H + off);
+                rs[u] = rstd[r + 4 * u];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] += bf2f(db[u][j]) * bf2f(xb[u][j]) * rs[u];
+        }
+        for (; r < r1; r += 4) {
+            const bf16x8 xb = *reinterpret_cast<const bf16x8*>(x + r * H + off);
+            const bf16x8 db = *reinterpret_cast<const bf16x8*>(dy + r * H + off);
+            const float rs = rstd[r];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] += bf2f(db[j]) * bf2f(xb[j]) * rs;
+        }
+    }
+    if (rl > 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[rl - 1][cg][j] = acc[j];
+    }
+    __syncthreads();
+    if (rl == 0 && live) {
+        f32x4 o[2];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j >> 2][j & 3] = acc[j] + red[0][cg][j] + red[1][cg][j] + red[2][cg][j];
+        float* p = part + (int64_t)blockIdx.y * H + off;
+        *reinterpret_cast<f32x4*>(p) = o[0];
+        *reinterpret_cast<f32x4*>(p + 4) = o[1];
+    }
+}
+
+// Stage 2 of every deterministic reduction: out[g][c] += part[g][0][c] + part[g][1][c] + ... (ascending), one thread per
+// four columns; grid (ceil(width/4/256), groups).  The loads of a thread are independent, only the additions chain.
+__global__ __launch_bounds__(256) void ordered_partial_sum_kernel(const float* __restrict__ part, float* __restrict__ out,
+                                                                  int n_part, int width) {
+    const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (c >= width) return;
+    const float* p = part + (int64_t)blockIdx.y * n_part * width + c;
+    f32x4 tot = *reinterpret_cast<const f32x4*>(p);
+    int s = 1;
+    for (; s + 8 <= n_part; s += 8) {
+        f32x4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4*>(p + (int64_t)(s + u) * width);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) tot += v[u];
+    }
+    for (; s < n_part; ++s) tot += *reinterpret_cast<const f32x4*>(p + (int64_t)s * width);
+    float* o = out + (int64_t)blockIdx.y * width + c;   // out: scalar accesses, the caller's buffer need not be 16-byte aligned
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] += tot[j];
+}
+
+// ln_mod backward with per-wave partials: ln_mod_bwd_kernel's token walk (dhidden bit for bit); wave w of frame f stores
+// its dshift | dscale sums at part[f][w][2H].  Every wave below waves_per_frame owns at least one token.
+template <int NCH>
+__global__ __launch_bounds__(256) void ln_mod_bwd_part_kernel(const bf16* __restrict__ dv, const float* __restrict__ xhat,
+                                                              const float* __restrict__ rstd_in, const bf16* __restrict__ mod,
+                                                              const int32_t* __restrict__ dst_row, bf16* __restrict__ dhidden,
+                                                              float* __restrict__ part, int ntok, int H, int tok_per_wave,
+                                                              int waves_per_frame) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int f = blockIdx.y;
+    const bf16* scale = mod + (int64_t)f * 2 * H + H;
+    float dsh[NCH][8], dsc[NCH][8];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dsh[c][j] = dsc[c][j] = 0.f;
+    const int w = blockIdx.x * 4 + wave;
+    const int t0 = w * tok_per_wave;
+    for (int t = t0; t < min(t0 + tok_per_wave, ntok); ++t) {
+        const int64_t irow = ((int64_t)f * ntok + t);
+        float g[NCH][8], xh[NCH][8];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int off = (c * 64 + lane) * 8;
+            if (off < H) {
+                const bf16x8 d = *reinterpret_cast<const bf16x8*>(dv + irow * H + off);
+                const bf16x8 sc = *reinterpret_cast<const bf16x8*>(scale + off);
+                const f32x4 x0 = *reinterpret_cast<const f32x4*>(xhat + irow * H + off);
+                const f32x4 x1 = *reinterpret_cast<const f32x4*>(xhat + irow * H + off + 4);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float df = bf2f(d[j]);
+                    xh[c][j] = j < 4 ? x0[j & 3] : x1[j & 3];
+                    g[c][j] = df * (1.0f + bf2f(sc[j]));
+                    s1 += g[c][j];
+                    s2 += g[c][j] * xh[c][j];
+                    dsh[c][j] += df;
+                    dsc[c][j] += df * xh[c][j];
+                }
+            }
+        }
+        const float m1 = wave_sum(s1) / (float)H, m2 = wave_sum(s2) / (float)H;
+        const float rstd = rstd_in[irow];
+        bf16* o = dhidden + ((int64_t)dst_row[f] + t) * H;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int off = (c * 64 + lane) * 8;
+            if (off < H) {
+                bf16x8 ob;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ob[j] = f2bf(rstd * (g[c][j] - m1 - xh[c][j] * m2));
+                *reinterpret_cast<bf16x8*>(o + off) = ob;
+            }
+        }
+    }
+    if (w >= waves_per_frame) return;
+    float* p = part + ((int64_t)f * waves_per_frame + w) * 2 * H;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int off = (c * 64 + lane) * 8;
+        if (off < H) {
+            *reinterpret_cast<f32x4*>(p + off) = f32x4{dsh[c][0], dsh[c][1], dsh[c][2], dsh[c][3]};
+            *reinterpret_cast<f32x4*>(p + off + 4) = f32x4{dsh[c][4], dsh[c][5], dsh[c][6], dsh[c][7]};
+            *reinterpret_cast<f32x4*>(p + H + off) = f32x4{dsc[c][0], dsc[c][1], dsc[c][2], dsc[c][3]};
+            *reinterpret_cast<f32x4*>(p + H + off + 4) = f32x4{dsc[c][4], dsc[c][5], dsc[c][6], dsc[c][7]};
+        }
+    }
+}
+
+// embedding backward without atomics, three launches over an int32 workspace key[rows4] | order[rows4] | meta[rows][2]
+// (rows4 = rows rounded up to 4):
+//   1. key[r] = ids[r] for a kept, in-range row, else -1 (also the padding up to rows4);
+//   2. a wave per row counts the kept rows with a smaller id and the kept rows with its own id before it and in all:
+//      the row's place in the (id, row) order, order[place] = r (a permutation: one writer per slot); the first row of
+//      an id records meta = (place, count), every other row count 0;
+//   3. a workgroup per (first row of an id, 256 columns): 8 row slots x 32 column groups; slot s adds occurrences
+//      s, s+8, ... of the id in ascending row order, the slots are added 0..7 through LDS and the one writer of
+//      dtable[id][c] adds the total to the caller's value.  Ids that never occur get no workgroup past its first load.
+__global__ __launch_bounds__(256) void embed_det_key_kernel(const int64_t* __restrict__ ids, const uint8_t* __restrict__ keep,
+                                                            int32_t* __restrict__ key, int64_t rows, int64_t rows4,
+                                                            int64_t vocab) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows4) return;
+    int32_t k = -1;
+    if (r < rows && keep[r]) {
+        const int64_t id = ids[r];
+        if (id >= 0 && id < vocab) k = (int32_t)id;
+    }
+    key[r] = k;
+}
+
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void embed_det_rank_kernel(const int32_t* __restrict__ key, int32_t* __restrict__ order,
+                                                             int32_t* __restrict__ meta, int rows, int rows4) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int mine = key[r];
+    if (mine < 0) {
+        if (lane == 0) meta[2 * r] = 0, meta[2 * r + 1] = 0;
+        return;
+    }
+    int lt = 0, eqb = 0, eq = 0;
+    for (int i = lane * 4; i < rows4; i += 256) {
+        const int4 k = *reinterpret_cast<const int4*>(key + i);
+        const int kk[4] = {k.x, k.y, k.z, k.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            lt += (kk[j] >= 0 && kk[j] < mine);
+            eq += (kk[j] == mine);
+            eqb += (kk[j] == mine && i + j < r);
+        }
+    }
+    lt = wave_sum_i(lt), eq = wave_sum_i(eq), eqb = wave_sum_i(eqb);
+    if (lane == 0) {
+        order[lt + eqb] = r;
+        meta[2 * r] = lt;
+        meta[2 * r + 1] = eqb == 0 ? eq : 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void embed_det_sum_kernel(const int32_t* __restrict__ key, const int32_t* __restrict__ order,
+                                                            const int32_t* __restrict__ meta, const bf16* __restrict__ dseq,
+                                                            float* __restrict__ dtable, int H) {
+    __shared__ float red[7][32][9];
+    const int r = blockIdx.x;
+    const int count = meta[2 * r + 1];
+    if (count == 0) return;   // the whole workgroup: not the first kept row of its id
+    const int32_t* occ = order + meta[2 * r];
+    const int cg = threadIdx.x & 31, slot = threadIdx.x >> 5;
+    const int off = (blockIdx.y * 32 + cg) * 8;
+    const bool live = off < H;
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    if (live) {
+        int k = slot;
+        for (; k + 24 < count; k += 32) {
+            bf16x8 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const bf16x8*>(dseq + (int64_t)occ[k + 8 * u] * H + off);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] += bf2f(v[u][j]);
+        }
+        for (; k < count; k += 8) {
+            const bf16x8 v = *reinterpret_cast<const bf16x8*>(dseq + (int64_t)occ[k] * H + off);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] += bf2f(v[j]);
+        }
+    }
+    if (slot > 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[slot - 1][cg][j] = acc[j];
+    }
+    __syncthreads();
+    if (slot == 0 && live) {
+        float* o = dtable + (int64_t)key[r] * H + off;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float t = acc[j];
+#pragma unroll
+            for (int s = 0; s < 7; ++s) t += red[s][cg][j];
+            o[j] += t;
+        }
+    }
+}
+
 // ---- gather the 16-wide patch vectors of a frame stack: patches[f*ntok+t][e] (bf16) ------------------
 __global__ void patchify_kernel(const bf16* __restrict__ x, bf16* __restrict__ patches, int n_frames, int C, int h,
                                 int w) {
@@ -875,6 +1128,110 @@ VGPT_EXPORT int vgpt_embed_bwd(const int64_t* ids, const uint8_t* keep, const vo
     hipLaunchKernelGGL(embed_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, ids, keep, (const bf16*)dseq,
                        dtable, rows, (int)H, vocab);
     LAUNCH_OK("vgpt_embed_bwd");
+}
+
+// ---- deterministic twins: same arguments plus a workspace, same results up to the order of the fp32 additions ----
+// strips of the rmsnorm dw reduction: vgpt_rmsnorm_bwd's own split, a function of the row count alone
+static void rmsnorm_det_strips(int64_t rows, int* rps, int* strips) {
+    const int want = (int)std::min<int64_t>(cdiv(rows, 4), 128);
+    *rps = (int)cdiv(rows, want);
+    *strips = (int)cdiv(rows, *rps);
+}
+
+VGPT_EXPORT int64_t vgpt_rmsnorm_bwd_det_workspace_bytes(int64_t rows, int64_t H) {
+    if (rows < 0 || H < 0) return -1;
+    return std::min<int64_t>(cdiv(rows, 4), 128) * H * (int64_t)sizeof(float);   // >= strips * H, monotonic in rows
+}
+
+VGPT_EXPORT int vgpt_rmsnorm_bwd_det(const void* x, const void* w, const void* dy, const void* dres, void* dx, float* dw,
+                                     float* rstd_ws, int64_t rows, int64_t H, float eps, float* ws, int64_t ws_floats,
+                                     void* stream) {
+    VGPT_REQUIRE(x && w && dy && dx && dw && rstd_ws && ws, VGPT_ERR_INVALID, "vgpt_rmsnorm_bwd_det: null pointer");
+    VGPT_REQUIRE(rows >= 0 && H > 0 && H % 8 == 0 && H <= 4096, VGPT_ERR_UNSUPPORTED,
+                 "vgpt_rmsnorm_bwd_det: H must be a multiple of 8 and <= 4096");
+    VGPT_REQUIRE(ws_floats * (int64_t)sizeof(float) >= vgpt_rmsnorm_bwd_det_workspace_bytes(rows, H), VGPT_ERR_INVALID,
+                 "vgpt_rmsnorm_bwd_det: workspace smaller than vgpt_rmsnorm_bwd_det_workspace_bytes(rows, H)");
+    VGPT_REQUIRE(((uintptr_t)ws & 15) == 0, VGPT_ERR_UNSUPPORTED, "vgpt_rmsnorm_bwd_det: workspace must be 16-byte aligned");
+    if (rows == 0) return VGPT_OK;
+    int grid = (int)std::min<int64_t>(cdiv(rows, 4), 256 * 8);
+    hipStream_t s = (hipStream_t)stream;
+#define RB_CASE(N)                                                                                                \
+    case N:                                                                                                       \
+        hipLaunchKernelGGL(rmsnorm_bwd_dx_kernel<N>, dim3(grid), dim3(256), 0, s, (const bf16*)x, (const bf16*)w, \
+                           (const bf16*)dy, (const bf16*)dres, (bf16*)dx, rstd_ws, rows, (int)H, eps);            \
+        break;
+    switch ((int)cdiv(H, 512)) { RB_CASE(1) RB_CASE(2) RB_CASE(3) RB_CASE(4) RB_CASE(5) RB_CASE(6) RB_CASE(7) RB_CASE(8) }
+#undef RB_CASE
+    int rps, strips;
+    rmsnorm_det_strips(rows, &rps, &strips);
+    hipLaunchKernelGGL(rmsnorm_bwd_dw_part_kernel, dim3((unsigned)cdiv(H / 8, 128), (unsigned)strips), dim3(512), 0, s,
+                       (const bf16*)x, (const bf16*)dy, rstd_ws, ws, rows, (int)H, rps);
+    hipLaunchKernelGGL(ordered_partial_sum_kernel, dim3((unsigned)cdiv(H / 4, 256), 1), dim3(256), 0, s, ws, dw, strips,
+                       (int)H);
+    LAUNCH_OK("vgpt_rmsnorm_bwd_det");
+}
+
+// tokens per wave of the deterministic ln_mod backward: at most 64 waves (partials) per frame, a function of ntok alone
+static int ln_mod_det_tpw(int64_t ntok) { return (int)std::max<int64_t>(1, cdiv(ntok, 64)); }
+
+VGPT_EXPORT int64_t vgpt_ln_mod_bwd_det_workspace_bytes(int64_t n_frames, int64_t ntok, int64_t H) {
+    if (n_frames < 0 || ntok < 0 || H < 0) return -1;
+    return n_frames * std::min<int64_t>(ntok, 64) * 2 * H * (int64_t)sizeof(float);   // >= waves per frame, monotonic
+}
+
+VGPT_EXPORT int vgpt_ln_mod_bwd_det(const void* dv, const float* xhat, const float* rstd, const void* mod,
+                                    const int32_t* dst_row, void* dhidden, float* dmod, int n_frames, int ntok, int64_t H,
+                                    float* ws, int64_t ws_floats, void* stream) {
+    VGPT_REQUIRE(dv && xhat && rstd && mod && dst_row && dhidden && dmod && ws, VGPT_ERR_INVALID,
+                 "vgpt_ln_mod_bwd_det: null pointer");
+    VGPT_REQUIRE(n_frames >= 0 && ntok > 0 && H > 0 && H % 8 == 0 && H <= 4096, VGPT_ERR_UNSUPPORTED,
+                 "vgpt_ln_mod_bwd_det: bad shape");
+    VGPT_REQUIRE(ws_floats * (int64_t)sizeof(float) >= vgpt_ln_mod_bwd_det_workspace_bytes(n_frames, ntok, H),
+                 VGPT_ERR_INVALID,
+                 "vgpt_ln_mod_bwd_det: workspace smaller than vgpt_ln_mod_bwd_det_workspace_bytes(n_frames, ntok, H)");
+    VGPT_REQUIRE(((uintptr_t)ws & 15) == 0, VGPT_ERR_UNSUPPORTED, "vgpt_ln_mod_bwd_det: workspace must be 16-byte aligned");
+    if (n_frames == 0) return VGPT_OK;
+    const int tpw = ln_mod_det_tpw(ntok);
+    const int wpf = (int)cdiv(ntok, tpw);   // waves (partials) per frame, <= min(ntok, 64)
+    dim3 grid((unsigned)cdiv(wpf, 4), n_frames);
+    hipStream_t s = (hipStream_t)stream;
+#define LB_CASE(N)                                                                                              \
+    case N:                                                                                                     \
+        hipLaunchKernelGGL(ln_mod_bwd_part_kernel<N>, grid, dim3(256), 0, s, (const bf16*)dv, xhat, rstd,       \
+                           (const bf16*)mod, dst_row, (bf16*)dhidden, ws, ntok, (int)H, tpw, wpf);              \
+        break;
+    switch ((int)cdiv(H, 512)) { LB_CASE(1) LB_CASE(2) LB_CASE(3) LB_CASE(4) LB_CASE(5) LB_CASE(6) LB_CASE(7) LB_CASE(8) }
+#undef LB_CASE
+    hipLaunchKernelGGL(ordered_partial_sum_kernel, dim3((unsigned)cdiv(2 * H / 4, 256), n_frames), dim3(256), 0, s, ws, dmod,
+                       wpf, (int)(2 * H));
+    LAUNCH_OK("vgpt_ln_mod_bwd_det");
+}
+
+VGPT_EXPORT int64_t vgpt_embed_bwd_det_workspace_bytes(int64_t rows) {
+    if (rows < 0) return -1;
+    return (2 * cdiv(rows, 4) * 4 + 2 * rows) * (int64_t)sizeof(int32_t);   // key[rows4] | order[rows4] | meta[rows][2]
+}
+
+VGPT_EXPORT int vgpt_embed_bwd_det(const int64_t* ids, const uint8_t* keep, const void* dseq, float* dtable, int64_t rows,
+                                   int64_t H, int64_t vocab, int32_t* ws, int64_t ws_ints, void* stream) {
+    VGPT_REQUIRE(ids && keep && dseq && dtable && ws, VGPT_ERR_INVALID, "vgpt_embed_bwd_det: null pointer");
+    VGPT_REQUIRE(rows >= 0 && rows < (1ll << 30) && vocab >= 0 && vocab < (1ll << 31), VGPT_ERR_INVALID,
+                 "vgpt_embed_bwd_det: bad argument");
+    VGPT_REQUIRE(H > 0 && H % 8 == 0, VGPT_ERR_UNSUPPORTED, "vgpt_embed_bwd_det: H must be a multiple of 8");
+    VGPT_REQUIRE(ws_ints * (int64_t)sizeof(int32_t) >= vgpt_embed_bwd_det_workspace_bytes(rows), VGPT_ERR_INVALID,
+                 "vgpt_embed_bwd_det: workspace smaller than vgpt_embed_bwd_det_workspace_bytes(rows)");
+    VGPT_REQUIRE(((uintptr_t)ws & 15) == 0, VGPT_ERR_UNSUPPORTED, "vgpt_embed_bwd_det: workspace must be 16-byte aligned");
+    if (rows == 0) return VGPT_OK;
+    const int64_t rows4 = cdiv(rows, 4) * 4;
+    int32_t *key = ws, *order = ws + rows4, *meta = ws + 2 * rows4;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(embed_det_key_kernel, dim3((unsigned)cdiv(rows4, 256)), dim3(256), 0, s, ids, keep, key, rows, rows4,
+                       vocab);
+    hipLaunchKernelGGL(embed_det_rank_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, s, key, order, meta, (int)rows,
+                       (int)rows4);
+    hipLaunchKernelGGL(embed_det_sum_kernel, dim3((unsigned)rows, (unsigned)cdiv(H / 8, 32)), dim3(256), 0, s, key, order,
+                       meta, (const bf16*)dseq, dtable, (int)H);
+    LAUNCH_OK("vgpt_embed_bwd_det");
 }
 
 VGPT_EXPORT int vgpt_patchify(const void* x, void* patches, int n_frames, int C, int h, int w, void* stream) {

@@ -93,9 +93,21 @@ def act_bwd(pre, dy, act):
 
 
 _rstd_ws = {}
+_det_ws = {}
 
 
-def rmsnorm_bwd(x, w, dy, dx, dw, eps, dres=None):
+def _det_workspace(device, n_bytes: int) -> torch.Tensor:
+    """The workspace of the deterministic reductions (vgpt_*_det): fp32 words, one per device, grown on demand."""
+    need = (int(n_bytes) + 3) // 4
+    ws = _det_ws.get(device)
+    if ws is None or ws.numel() < need:
+        ws = _det_ws[device] = torch.empty(max(need, 1 << 16), dtype=F32, device=device)
+    return ws
+
+
+def rmsnorm_bwd(x, w, dy, dx, dw, eps, dres=None, deterministic=False):
+    """deterministic: dw is added strip by strip in a fixed order (vgpt_rmsnorm_bwd_det) instead of with fp32 atomics;
+    dx is the same either way."""
     _chk(x, BF16, "rmsnorm_bwd.x"); _chk(dy, BF16, "rmsnorm_bwd.dy"); _chk(dx, BF16, "rmsnorm_bwd.dx")
     _chk(dw, F32, "rmsnorm_bwd.dw")
     H = x.shape[-1]
@@ -103,6 +115,11 @@ def rmsnorm_bwd(x, w, dy, dx, dw, eps, dres=None):
     ws = _rstd_ws.get(x.device)
     if ws is None or ws.numel() < rows:
         ws = _rstd_ws[x.device] = torch.empty(max(rows, 1), dtype=F32, device=x.device)
+    if deterministic:
+        part = _det_workspace(x.device, _lib.load().vgpt_rmsnorm_bwd_det_workspace_bytes(rows, H))
+        call("vgpt_rmsnorm_bwd_det", x.data_ptr(), w.data_ptr(), dy.data_ptr(), _ptr(dres), dx.data_ptr(), dw.data_ptr(),
+             ws.data_ptr(), rows, H, float(eps), part.data_ptr(), part.numel(), _stream())
+        return dx
     call("vgpt_rmsnorm_bwd", x.data_ptr(), w.data_ptr(), dy.data_ptr(), _ptr(dres), dx.data_ptr(), dw.data_ptr(),
          ws.data_ptr(), rows, H, float(eps), _stream())
     return dx
@@ -161,13 +178,26 @@ def ln_mod_fwd(hidden2d, src_row, mod, v_out, xhat, rstd, ntok, eps=1e-6):
          rstd.data_ptr(), nf, ntok, hidden2d.shape[-1], float(eps), _stream())
 
 
-def ln_mod_bwd(dv, xhat, rstd, mod, dst_row, dhidden2d, dmod, ntok):
+def ln_mod_bwd(dv, xhat, rstd, mod, dst_row, dhidden2d, dmod, ntok, deterministic=False):
+    """deterministic: dmod is added wave by wave in a fixed order (vgpt_ln_mod_bwd_det) instead of with fp32 atomics."""
     nf = dst_row.numel()
+    if deterministic:
+        H = dhidden2d.shape[-1]
+        part = _det_workspace(dv.device, _lib.load().vgpt_ln_mod_bwd_det_workspace_bytes(nf, ntok, H))
+        call("vgpt_ln_mod_bwd_det", dv.data_ptr(), xhat.data_ptr(), rstd.data_ptr(), mod.data_ptr(), dst_row.data_ptr(),
+             dhidden2d.data_ptr(), dmod.data_ptr(), nf, ntok, H, part.data_ptr(), part.numel(), _stream())
+        return
     call("vgpt_ln_mod_bwd", dv.data_ptr(), xhat.data_ptr(), rstd.data_ptr(), mod.data_ptr(), dst_row.data_ptr(),
          dhidden2d.data_ptr(), dmod.data_ptr(), nf, ntok, dhidden2d.shape[-1], _stream())
 
 
-def embed_bwd(ids, keep, dseq2d, dtable):
+def embed_bwd(ids, keep, dseq2d, dtable, deterministic=False):
+    """deterministic: one writer per table element adds its rows in a fixed order (vgpt_embed_bwd_det), no atomics."""
+    if deterministic:
+        part = _det_workspace(dseq2d.device, _lib.load().vgpt_embed_bwd_det_workspace_bytes(ids.numel()))
+        call("vgpt_embed_bwd_det", ids.data_ptr(), keep.data_ptr(), dseq2d.data_ptr(), dtable.data_ptr(), ids.numel(),
+             dseq2d.shape[-1], dtable.shape[0], part.data_ptr(), part.numel(), _stream())
+        return
     call("vgpt_embed_bwd", ids.data_ptr(), keep.data_ptr(), dseq2d.data_ptr(), dtable.data_ptr(), ids.numel(),
          dseq2d.shape[-1], dtable.shape[0], _stream())
 

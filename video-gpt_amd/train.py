@@ -150,7 +150,8 @@ class Stage1Trainer:
                  lora_alpha: Optional[float] = None, lora_target_modules=LORA_TARGETS,
                  gradient_accumulation_steps: int = 1, use_ema: bool = False, ema_decay: float = 0.9999,
                  lr_num_training_steps: Optional[int] = None, lr_num_cycles: Optional[float] = None,
-                 lr_power: float = 1.0, sequence_parallel: bool = False, sp_group=None, check_sp_inputs: bool = True):
+                 lr_power: float = 1.0, sequence_parallel: bool = False, sp_group=None, check_sp_inputs: bool = True,
+                 deterministic: bool = False):
         """lr_scheduler / lr_warmup_steps / lr_num_training_steps / lr_num_cycles / lr_power: diffusers' get_scheduler
         (train_x1_stage1_noiseinput.py:279-283, 513-521; the scripts use constant_with_warmup), one of LR_SCHEDULERS: the
         k-th optimizer step (k = 0, 1, ...) runs at lr * lr_factor(name, k * lr_scheduler_steps_per_optimizer_step, ...);
@@ -200,7 +201,11 @@ class Stage1Trainer:
         world / P data-parallel replicas of P ranks; the update equals the P = 1 update on the same clips up to summation
         order (unlike the reference, whose decoder gradients come out scaled 1 / P).  check_sp_inputs:
         every sharded step() first all-gathers a 16-byte digest of (input_ids, t, x1.shape) over the group and raises on
-        every rank when they differ; False skips that collective."""
+        every rank when they differ; False skips that collective.
+        deterministic: the three reductions of the step that add with fp32 atomics (RMSNorm gain gradients, the final
+        layer's dshift / dscale, the embedding-table gradient) run their fixed-order twins (vgpt_*_det), which makes the
+        step a pure function of its inputs: same inputs, build, world size and collective library give the same bits
+        (DESIGN.md §6d).  Composes with every other option; nothing to do in a forward-only trainer."""
         model._check_ready()
         if hasattr(model, "release_engines"):
             model.release_engines()          # a sampler engine cached on the model holds GBs the trainer's buffers want
@@ -238,6 +243,7 @@ class Stage1Trainer:
         self.gradient_checkpointing = (bool(getattr(model.llm, "gradient_checkpointing", False))
                                        if gradient_checkpointing is None else bool(gradient_checkpointing))
         self.forward_only = forward_only
+        self.deterministic = bool(deterministic)
         self.max_grad_norm = max_grad_norm
         self.input_noise = input_noise
         self.pack_padding = pack_padding
@@ -584,11 +590,12 @@ class Stage1Trainer:
                 w.wait()
 
     @classmethod
-    def for_evaluation(cls, model):
-        """A forward-only trainer cached on the model (no gradient buckets, no optimizer state)."""
+    def for_evaluation(cls, model, deterministic: bool = False):
+        """A forward-only trainer cached on the model (no gradient buckets, no optimizer state; `deterministic` is kept on
+        a new one and changes nothing: the forward pass has no order-dependent sum)."""
         tr = getattr(model, "_vgpt_eval_trainer", None)
         if tr is None:
-            tr = cls(model, forward_only=True)
+            tr = cls(model, forward_only=True, deterministic=deterministic)
             object.__setattr__(model, "_vgpt_eval_trainer", tr)
         return tr
 
@@ -816,6 +823,7 @@ class Stage1Trainer:
             return loss
         # ---------------- backward ----------------
         g = self.grads
+        det = self.deterministic     # the fixed-order twins of the three reductions that add with atomics
         self.small_bucket.zero_()
         dy16 = T.unpatchify_bwd(dpred)                                      # (Tn, 16)
         T.matmul(dy16, v, out=g["final_layer.linear.weight"], ta=True)     # dWf = dy16^T v
@@ -823,7 +831,7 @@ class Stage1Trainer:
         dv = T.matmul(dy16, fl.weight)                                      # (Tn, H)
         dnrm = self._buf("dnrm", (M, H)); dnrm.zero_()
         dmod = torch.zeros(nf, 2 * H, dtype=F32, device=self.dev)
-        T.ln_mod_bwd(dv, xhat, rstd, mod, prep["x_rows"], dnrm, dmod, ntok)
+        T.ln_mod_bwd(dv, xhat, rstd, mod, prep["x_rows"], dnrm, dmod, ntok, deterministic=det)
         if head is not None:
             dyin = T.unpatchify_bwd(dpred_in)                                # (nfc * ntok, 16)
             T.matmul(dyin, vin, out=g["input_final_layer.weight"], ta=True)
@@ -832,7 +840,7 @@ class Stage1Trainer:
         dh = self._buf("dh", (Ms, H)); dh_b = self._buf("dh_b", (Ms, H))
         # sharded: every rank keeps its own rows of dnrm (Gather.backward, LVM/utils.py:163-169): no exchange
         T.rmsnorm_bwd(hbuf[nl], m.llm.norm.weight, dnrm if sp is None else dnrm[r0:r1], dh, g["llm.norm.weight"],
-                      m.llm.norm.variance_epsilon)
+                      m.llm.norm.variance_epsilon, deterministic=det)
         # adaLN + t_embedder
         T.matmul(dmod, st, out=g["final_layer.adaLN_modulation.1.weight"], ta=True)
         T.colsum(dmod, g["final_layer.adaLN_modulation.1.bias"])
@@ -867,7 +875,7 @@ class Stage1Trainer:
             T.linear_dx(dgu, mlp.gate_up_proj.weight, sw, out=dn)
             T.rmsnorm_bwd(h2[k], layer.post_attention_layernorm.weight, dn, dh_b,
                           g[f"llm.layers.{li}.post_attention_layernorm.weight"],
-                          layer.post_attention_layernorm.variance_epsilon, dres=dh)       # dh2
+                          layer.post_attention_layernorm.variance_epsilon, dres=dh, deterministic=det)   # dh2
             T.linear_dw(dh_b, ctx[k], sa, sb, g[names[1]])                             # dW_o
             T.linear_dx(dh_b, at.o_proj.weight, sw, out=dctx)
             if sp is None:
@@ -887,7 +895,7 @@ class Stage1Trainer:
             T.linear_dx(dqkv, at.qkv_proj.weight, sw, out=dn)
             T.rmsnorm_bwd(hbuf[li], layer.input_layernorm.weight, dn, dh,
                           g[f"llm.layers.{li}.input_layernorm.weight"], layer.input_layernorm.variance_epsilon,
-                          dres=dh_b)                                                     # dh (layer input)
+                          dres=dh_b, deterministic=det)                                  # dh (layer input)
             if acc_mode is not None:     # right behind this layer's last dW, where its bucket is complete
                 T.grad_accumulate(self._accumulators()[1][li], self.layer_buckets[li], acc_mode)
             if exchange and self.world > 1 and not self.skip_allreduce and self.overlap_allreduce:
@@ -906,7 +914,7 @@ class Stage1Trainer:
         self._patch_bwd("x_embedder", T.gather_rows(dseq, prep["x_rows"], ntok), xt)
         if cl is not None:
             self._patch_bwd("input_x_embedder", T.gather_rows(dseq, prep["c_rows"], ntok), cl)
-        T.embed_bwd(prep["ids"].view(-1), prep["keep"], dseq, g["llm.embed_tokens.weight"])
+        T.embed_bwd(prep["ids"].view(-1), prep["keep"], dseq, g["llm.embed_tokens.weight"], deterministic=det)
         if acc_mode is not None:
             T.grad_accumulate(self._accumulators()[0], self.small_bucket, acc_mode)
         if exchange and self.world > 1 and not self.skip_allreduce:
@@ -940,17 +948,18 @@ class Stage1Trainer:
         hbuf, n1, qkv, ctx, h2, n2, gu, act, lse = (f[k] for k in ("hbuf", "n1", "qkv", "ctx", "h2", "n2", "gu", "act", "lse"))
         u_q, u_o, sv, ck, rp, ls = f["u_q"], f["u_o"], f["sv"], f["ck"], self.lora_rp, self.lora_scale
         lq, lo = f["lq"], f["lo"]
+        det = self.deterministic     # the discarded dgain / dmod sums too: one rule for every path
         dy16 = T.unpatchify_bwd(f["dpred"])                                  # (Tn, 16)
         dv = T.matmul(dy16, f["fl"].weight)                                  # (Tn, H)
         dnrm = self._buf("dnrm", (M, H)); dnrm.zero_()
         dmod = self._buf("dmod_scratch", (nf, 2 * H), F32); dmod.zero_()     # feeds adaLN only: discarded
-        T.ln_mod_bwd(dv, f["xhat"], f["rstd"], f["mod"], prep["x_rows"], dnrm, dmod, ntok)
+        T.ln_mod_bwd(dv, f["xhat"], f["rstd"], f["mod"], prep["x_rows"], dnrm, dmod, ntok, deterministic=det)
         if f["head"] is not None:
             dyin = T.unpatchify_bwd(f["dpred_in"])
             dnrm.index_copy_(0, prep["c_idx"], T.matmul(dyin, f["head"].weight))
         dgain = self._buf("dgain_scratch", (H,), F32); dgain.zero_()         # gain gradients of the frozen norms: discarded
         dh = self._buf("dh", (M, H)); dh_b = self._buf("dh_b", (M, H))
-        T.rmsnorm_bwd(hbuf[nl], m.llm.norm.weight, dnrm, dh, dgain, m.llm.norm.variance_epsilon)
+        T.rmsnorm_bwd(hbuf[nl], m.llm.norm.weight, dnrm, dh, dgain, m.llm.norm.variance_epsilon, deterministic=det)
         dact = self._buf("dact", (M, I)); dgu = self._buf("dgu", (M, 2 * I)); dn = self._buf("dn", (M, H))
         dctx = self._buf("dctx", (M, nq * hd)); dqkv = self._buf("dqkv", (M, (nq + 2 * nk) * hd))
         delta = self._buf("delta", (B, nq, L), F32)
@@ -967,7 +976,7 @@ class Stage1Trainer:
             T.silu_mul_bwd(gu[k], dact, dgu, mlp.act)
             T.linear_dx(dgu, mlp.gate_up_proj.weight, None, out=dn)
             T.rmsnorm_bwd(h2[k], layer.post_attention_layernorm.weight, dn, dh_b, dgain,
-                          layer.post_attention_layernorm.variance_epsilon, dres=dh)       # dh2
+                          layer.post_attention_layernorm.variance_epsilon, dres=dh, deterministic=det)   # dh2
             T.linear_dx(dh_b, at.o_proj.weight, None, out=dctx)
             if lo:
                 w, gr = self._lora_w[(li, "o_proj")], self._lora_g[(li, "o_proj")]
@@ -989,7 +998,7 @@ class Stage1Trainer:
             if lq:
                 LO.lora_up_add(dn, du, w["A"], s_is_rp_by_n=True)
             T.rmsnorm_bwd(hbuf[li], layer.input_layernorm.weight, dn, dh, dgain, layer.input_layernorm.variance_epsilon,
-                          dres=dh_b)                                                     # dh (layer input)
+                          dres=dh_b, deterministic=det)                                  # dh (layer input)
         if f["acc_mode"] is not None:
             T.grad_accumulate(self._accumulators()[0], self.lora_bucket, f["acc_mode"])
         if f["exchange"] and self.world > 1 and not self.skip_allreduce:
