@@ -472,6 +472,33 @@ int vgpt_conv1x1_bx3_fwd(const float* x, const void* packed, const float* bias, 
 /* In-place softmax over the KEY axis of S^T (N, keys, queries) with pre-scale (mid-block attention). */
 int vgpt_col_softmax(float* s, int N, int keys, int queries, float scale, void* stream);
 
+/* Fused mid-block attention (diffusers' `Attention` of the VAE mid-block, one head over the HW positions of a frame,
+ * as reached from LVM/pipeline.py:110-117 encode and :558-590 decode), exact fp32, one pass with an online softmax: the
+ * (HW, HW) score matrix is never stored, there is no workspace and there are no atomics.
+ *   s[j][i] = scale * sum_c k[c][j] q[c][i]   (j = key, i = query)
+ *   p[.][i] = softmax over j
+ *   o[c][i] = sum_j v[c][j] p[j][i]
+ * Layout: q, k, v, o are fp32 in the VAE's [n][c][pos] layout with one shared pair of strides: element (n, c, p) is at
+ * base + n * batch_stride + c * ld + p (a contiguous NCHW activation: ld = HW, batch_stride = C * HW).  V is staged with
+ * 16-byte accesses when ld % 4 == 0, batch_stride % 4 == 0 and v is 16-byte aligned, with scalar ones otherwise; both
+ * give the same bits.
+ * Tiles: a workgroup owns VGPT_VAE_ATTN_TQ queries of one image (two halves of 32) and walks the keys
+ * VGPT_VAE_ATTN_TK at a time (N * ceil(HW / TQ) workgroups); key tails are masked to -inf before the maximum, query
+ * tails are not stored.
+ * Rounding points: both products run on v_mfma_f32_32x32x2_f32, bit for bit fp32 FMA chains.  A score is four chains of
+ * C/4 channels (ascending) summed as ((c0 + c1) + c2) + c3, then * scale; per key tile x - m with the running maximum m,
+ * exp as v_exp_f32((x - m) * log2 e), l = l * a + sum(p) and o = o * a with a = exp(m_old - m_new), then an FMA chain
+ * over the tile's keys; o / l is an IEEE division at the end.  The result is a pure function of the inputs: two launches
+ * agree bit for bit, and a batch of N equals N single launches.
+ * Refusals: a null pointer, N < 0, HW <= 0, ld < HW, batch_stride < C * ld, scale <= 0 or o overlapping an input:
+ * VGPT_ERR_INVALID.  C not a multiple of 64 or above VGPT_VAE_ATTN_MAX_C (or ld >= 2^28, or 2^31 workgroups): VGPT_ERR_UNSUPPORTED;
+ * vgpt_last_error() names the value.  N == 0: VGPT_OK, nothing launched.  Capturable: no allocation, no sync. */
+#define VGPT_VAE_ATTN_TQ 64
+#define VGPT_VAE_ATTN_TK 32
+#define VGPT_VAE_ATTN_MAX_C 512
+int vgpt_vae_attn_fwd(const float* q, const float* k, const float* v, float* o, int64_t N, int C, int64_t HW,
+                      int64_t ld, int64_t batch_stride, float scale, void* stream);
+
 /* DiagonalGaussianDistribution.sample + latent scaling (LVM/pipeline.py:110-115):
  * z = (mean + exp(0.5*clamp(logvar,-30,20)) * noise - shift) * scaling.
  * moments: (N, 2*per_image) = [mean | logvar] per image; noise, z: (N, per_image). */

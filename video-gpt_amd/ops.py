@@ -1026,6 +1026,46 @@ def col_softmax(s: torch.Tensor, scale: float):
     return s
 
 
+VAE_ATTN_MAX_C = 512   # VGPT_VAE_ATTN_MAX_C (include/vgpt.h)
+
+
+def vae_attention_supported(C: int) -> bool:
+    """Channel counts vgpt_vae_attn_fwd was built for: multiples of 64 up to 512."""
+    return 64 <= C <= VAE_ATTN_MAX_C and C % 64 == 0
+
+
+def vae_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, out: Optional[torch.Tensor] = None):
+    """o = V softmax_keys(scale K^T Q): the VAE mid-block's single-head attention, fused, exact fp32, no score matrix
+    (include/vgpt.h, vgpt_vae_attn_fwd).  q, k, v: (N, C, H, W) or (N, C, HW) fp32 in the [n][c][pos] layout; the
+    positions of a channel are contiguous, and the channel and image strides are read off q and shared by all four."""
+    shape = tuple(q.shape)
+    if q.dim() not in (3, 4):
+        raise VgptError(f"vae_attention: expected (N, C, H, W) or (N, C, HW), got {shape}")
+    if out is None:
+        out = torch.empty_strided(shape, q.stride(), dtype=F32, device=q.device)
+    N, C = shape[:2]
+    HW = math.prod(shape[2:])
+    ld, bs = q.stride(1), q.stride(0)
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _chk(t, F32, f"vae_attention.{name}", contiguous=False)
+        if tuple(t.shape) != shape:
+            raise VgptError(f"vae_attention.{name}: shape {tuple(t.shape)} differs from q's {shape}")
+        if t.device != q.device:
+            raise VgptError(f"vae_attention.{name}: on {t.device}, q is on {q.device}")
+        st = t.stride()
+        if N * C * HW and (st[-1] != 1 or (t.dim() == 4 and shape[2] > 1 and st[2] != shape[3])):
+            raise VgptError(f"vae_attention.{name}: the positions of a channel must be contiguous (strides {st})")
+        if (C > 1 and st[1] != ld) or (N > 1 and st[0] != bs):
+            raise VgptError(f"vae_attention.{name}: strides {st} differ from q's {q.stride()}")
+    if N == 0 and HW > 0:
+        return out
+    if N == 1:
+        bs = max(bs, C * ld)
+    call("vgpt_vae_attn_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, C, HW, ld, bs, float(scale),
+         _stream())
+    return out
+
+
 def vae_sample(moments: torch.Tensor, noise: torch.Tensor, shift: float, scaling: float):
     _chk(moments, F32, "vae_sample.moments"); _chk(noise, F32, "vae_sample.noise")
     N = moments.shape[0]

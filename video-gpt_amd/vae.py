@@ -8,7 +8,8 @@ Interface mirror of what the reference touches (LVM/pipeline.py:87-117,558-590; 
 Execution: every Conv2d/Linear is `ops.conv2d` (implicit GEMM on the fp32 MFMA); GroupNorm+SiLU is
 never materialised (stats kernel + normalise-on-load prologue of the next conv); nearest upsampling is
 folded into the following conv's loader; the resnet skip / attention residual is the conv epilogue;
-the mid-block attention is Q K^T -> column softmax -> P V through the same conv kernel.
+the mid-block attention is Q K^T -> column softmax -> P V through the same conv kernel ("materialised") or one fused
+online-softmax kernel that never stores the score matrix ("fused", ops.vae_attention); `AutoencoderKL.attention_impl`.
 """
 from __future__ import annotations
 
@@ -24,6 +25,10 @@ from . import ops
 from .ops import VgptError
 
 F32 = torch.float32
+ATTENTION_IMPLS = ("auto", "materialised", "fused")
+# "auto" takes the fused kernel above this many positions: every frame up to 512x512 (HW <= 4096) keeps the bits of the
+# materialised path, everything larger stops allocating the (N, HW, HW) score tensor
+AUTO_FUSED_ABOVE_HW = 4096
 
 
 class _Norm(nn.Module):
@@ -84,14 +89,22 @@ class _Attention(nn.Module):
         self.to_q, self.to_k, self.to_v = nn.Linear(c, c), nn.Linear(c, c), nn.Linear(c, c)
         self.to_out = nn.ModuleList([nn.Linear(c, c), nn.Identity()])
 
-    def run(self, x, groups, eps, prec="fp32"):
+    def run(self, x, groups, eps, prec="fp32", attn="auto"):
         N, C, H, W = x.shape
         HW = H * W
+        if attn not in ATTENTION_IMPLS:
+            raise VgptError(f"unknown attention_impl {attn!r} ({' | '.join(ATTENTION_IMPLS)})")
+        if attn == "fused" and not ops.vae_attention_supported(C):
+            raise VgptError(f"attention_impl='fused': C = {C} is not a multiple of 64 up to {ops.VAE_ATTN_MAX_C}")
+        fused = attn == "fused" or (attn == "auto" and ops.vae_attention_supported(C) and HW > AUTO_FUSED_ABOVE_HW)
         st = ops.groupnorm_stats(x, groups, eps)
         gn = (st, self.group_norm.weight, self.group_norm.bias, groups, 0)
         q = _conv1(self.to_q, x, prec, gn=gn)   # (N, C, H, W) = [c][pos]
         k = _conv1(self.to_k, x, prec, gn=gn)
         v = _conv1(self.to_v, x, prec, gn=gn)
+        if fused:
+            o = ops.vae_attention(q, k, v, 1.0 / (C ** 0.5))
+            return _conv1(self.to_out[0], o, prec, resid=x)
         # S^T[key][query] = sum_c K[c][key] Q[c][query]: "weights" = K stored [c][key] (transposed), input = Q
         # (a 1x1 conv is pointwise, so the HW query positions keep their (H, W) tiling)
         st_ = ops.conv2d(q, k, ksize=1, cout=HW, w_transposed=True, ldw=HW, w_batch_stride=C * HW)   # (N, HW, H, W)
@@ -107,9 +120,9 @@ class _Mid(nn.Module):
         self.resnets = nn.ModuleList([_Resnet(c, c), _Resnet(c, c)])
         self.attentions = nn.ModuleList([_Attention(c)])
 
-    def run(self, x, groups, eps, prec="fp32"):
+    def run(self, x, groups, eps, prec="fp32", attn="auto"):
         x = self.resnets[0].run(x, groups, eps, prec)
-        x = self.attentions[0].run(x, groups, eps, prec)
+        x = self.attentions[0].run(x, groups, eps, prec, attn)
         return self.resnets[1].run(x, groups, eps, prec)
 
 
@@ -196,6 +209,10 @@ class AutoencoderKL(nn.Module):
         # MFMA, ~16 mantissa bits (the reference's torch/cuDNN default for these fp32 convolutions is TF32, 10 bits),
         # 1.8x faster; "fp32" = exact fp32 MFMA.  Both meet the same parity tolerances (tests/test_vae_gpu.py).
         self.conv_precision = "bf16x3"
+        # mid-block attention: "materialised" = K^T Q -> column softmax -> P V with the (N, HW, HW) score tensor in
+        # memory; "fused" = ops.vae_attention, no score tensor (C a multiple of 64 up to 512, VgptError otherwise);
+        # "auto" = fused exactly when C is supported and HW > 4096
+        self.attention_impl = "auto"
 
     @classmethod
     def from_pretrained(cls, path):
@@ -229,7 +246,7 @@ class AutoencoderKL(nn.Module):
             if hasattr(blk, "downsamplers"):
                 c = blk.downsamplers[0].conv
                 h = ops.conv2d(h, c.weight, c.bias, stride=2)       # 3 launches per frame: stays on the fp32 kernel
-        h = enc.mid_block.run(h, g, eps, pr)
+        h = enc.mid_block.run(h, g, eps, pr, self.attention_impl)
         st = ops.groupnorm_stats(h, g, eps)
         h = _conv3(enc.conv_out, h, pr, gn=(st, enc.conv_norm_out.weight, enc.conv_norm_out.bias, g, 1))
         moments = ops.conv2d(h, self.quant_conv.weight, self.quant_conv.bias, ksize=1)
@@ -241,7 +258,7 @@ class AutoencoderKL(nn.Module):
         g, eps, dec, pr = self.config.norm_num_groups, self.eps, self.decoder, self.conv_precision
         h = ops.conv2d(z.to(F32).contiguous(), self.post_quant_conv.weight, self.post_quant_conv.bias, ksize=1)
         h = _conv3(dec.conv_in, h, pr)
-        h = dec.mid_block.run(h, g, eps, pr)
+        h = dec.mid_block.run(h, g, eps, pr, self.attention_impl)
         for blk in dec.up_blocks:
             for r in blk.resnets:
                 h = r.run(h, g, eps, pr)
