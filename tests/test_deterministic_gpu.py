@@ -191,6 +191,24 @@ def test_lora(TR, stage1):
         _assert_equal(sa, sb, f"LoRA step {i}")
 
 
+def test_lora_optimizer_overlap_is_the_same_run(TR, stage1):
+    """The adapter update on the optimizer's stream against the inline one, to the bit (tests/test_lora_gpu.py bounds it)."""
+    def run(ov):
+        torch.manual_seed(11)
+        tr = _trainer(TR, stage1, lora_rank=4, overlap_optimizer=ov)
+        assert tr.overlap_optimizer == ov
+        gen = torch.Generator("cpu").manual_seed(48)
+        for k, v in tr.lora.items():          # lora_B away from its zero init, as in test_lora
+            if ".lora_B." in k:
+                v.copy_((torch.randn(v.shape, generator=gen) * 0.02).to(BF))
+        tr.lora_master.copy_(tr.lora_param)
+        return [_snapshot(tr, _step(tr, stage1, i)) for i in range(3)]
+    a, b = run(False), run(True)
+    assert float(a[0]["grad:lora"].abs().max()) > 0 and not torch.equal(a[0]["lora_param"], a[2]["lora_param"])
+    for i, (sa, sb) in enumerate(zip(a, b)):
+        _assert_equal(sa, sb, f"LoRA overlap step {i}")
+
+
 def test_flag_on_against_flag_off(TR, stage1):
     out = {}
     for det in (False, True):
@@ -238,12 +256,34 @@ def _dp_worker(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def _dp_job():
+def _sharded_overlap_worker(rank, world, port, q):
+    """dp_sharding="optimizer" with overlap_optimizer off and on, three steps each: what differs between the two runs."""
+    import os
+    os.environ.update(RANK=str(rank), LOCAL_RANK="0", WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    import torch.distributed as dist
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    p, batch, x1, x0, t, clean, x0i, ti = GC.stage1_case(R.TINY)
+    x1 = torch.randn(x1.shape, generator=torch.Generator("cpu").manual_seed(500 + rank))     # different data on every rank
+    case = dict(p=p, cls="LVMTraining", batch=_on_device(batch), args=(x1, x0, t, clean, x0i, ti))
+    TR = importlib.import_module("video-gpt_amd.train")
+    runs = {}
+    for ov in (False, True):
+        runs[ov], tr = _run(TR, case, steps=3, dp_sharding="optimizer", overlap_optimizer=ov)
+        assert tr._sharded and tr.overlap_optimizer == ov
+    moved = not torch.equal(runs[False][0]["state:master_small"], runs[False][2]["state:master_small"])
+    bad = [f"step {i}: {k}" for i, (sa, sb) in enumerate(zip(runs[False], runs[True]))
+           for k in sa.keys() | sb.keys() if k not in sa or k not in sb or not torch.equal(sa[k], sb[k])]
+    q.put((rank, bad, moved))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _dp_job(worker=_dp_worker):
     import torch.multiprocessing as mp
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=worker, args=(r, 2, port, q)) for r in range(2)]
     for p_ in procs:
         p_.start()
     try:
@@ -268,3 +308,9 @@ def test_two_data_parallel_ranks_twice():
     for k in sd0:
         assert np.array_equal(sd0[k], sd1[k]), f"{k}: rank 0 and rank 1 differ"
         assert np.array_equal(sd0[k], sd0b[k]), f"{k}: the two jobs differ"
+
+
+def test_sharded_optimizer_overlap_is_the_same_run():
+    for rank, bad, moved in _dp_job(_sharded_overlap_worker):
+        assert moved, f"rank {rank}: the chain does not move"
+        assert not bad, f"rank {rank}: overlap on / off differ in {bad[:8]} ({len(bad)})"

@@ -32,10 +32,11 @@ optimizer to DeepSpeed's bf16 AdamW (fp32 master weights).  Here:
 """
 from __future__ import annotations
 
+import json
 import math
 import os
 import weakref
-
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import torch
@@ -139,6 +140,18 @@ def wait_for_pending_update(model) -> None:
 
 def _state_dict_barrier(module, prefix, keep_vars):
     wait_for_pending_update(module)
+
+
+class _Bucket:
+    """One gradient bucket and everything the optimizer keeps for it.  key: "small", a decoder layer's index, or "lora";
+    names: its tensors in buffer order; numel: its unpadded length (the checkpoint layout); grad / param: the flat buffers
+    (zero-padded when sharded); master / m / v / ema: fp32 state, this rank's shard when sharded; acc: the fp32
+    accumulator of gradient accumulation.  What a mode does not have is None."""
+    __slots__ = ("key", "names", "numel", "grad", "param", "master", "m", "v", "ema", "acc")
+
+    def __init__(self, key, names, numel):
+        self.key, self.names, self.numel = key, names, numel
+        self.grad = self.param = self.master = self.m = self.v = self.ema = self.acc = None
 
 
 class Stage1Trainer:
@@ -289,6 +302,8 @@ class Stage1Trainer:
         self._ws = {}
         self.last = {}
         self.grads: Dict[str, torch.Tensor] = {}
+        self.buckets: List[_Bucket] = []      # update / read order: the small bucket, then layers 0 .. L-1; LoRA: the one
+        #                                       adapter bucket; none in a forward-only trainer
         self.lora_rank = None
         self.lora: Dict[str, torch.Tensor] = {}
         if lora_rank is not None:
@@ -296,66 +311,73 @@ class Stage1Trainer:
             return
         if forward_only:
             return
-        L = self.cfg.num_hidden_layers
-        # ---- gradient storage: one flat bf16 bucket per decoder layer + one fp32 bucket for the rest ----
+        # ---- one record per gradient bucket: a flat bf16 bucket per decoder layer + one fp32 bucket for the rest ----
         self.layer_names = [[f"llm.layers.{i}.self_attn.qkv_proj.weight", f"llm.layers.{i}.self_attn.o_proj.weight",
                              f"llm.layers.{i}.mlp.gate_up_proj.weight", f"llm.layers.{i}.mlp.down_proj.weight"]
-                            for i in range(L)]
-        self.layer_buckets = []
-        self._bucket_numel = []       # unpadded lengths of the layer buckets: the checkpoint layout
-        for names in self.layer_names:
-            n = sum(self.params[k].numel() for k in names)
-            self._bucket_numel.append(n)
-            flat = torch.zeros(self._padded(n), dtype=BF16, device=self.dev)
-            o = 0
-            for k in names:
-                sz = self.params[k].numel()
-                self.grads[k] = flat[o:o + sz].view(self.params[k].shape)
-                o += sz
-            self.layer_buckets.append(flat)
+                            for i in range(self.cfg.num_hidden_layers)]
         big = {k for names in self.layer_names for k in names}
-        small = [k for k in self.params if k not in big]
-        n_small = sum(self.params[k].numel() for k in small)
-        self._small_numel = n_small
-        self.small_bucket = torch.zeros(self._padded(n_small), dtype=F32, device=self.dev)
-        o = 0
-        for k in small:
-            sz = self.params[k].numel()
-            self.grads[k] = self.small_bucket[o:o + sz].view(self.params[k].shape)
-            o += sz
+        self.small_names = [k for k in self.params if k not in big]
+        layers = [self._make_bucket(i, names, BF16) for i, names in enumerate(self.layer_names)]
+        self.buckets = [self._make_bucket("small", self.small_names, F32)] + layers     # update / read order
+        # ---- optimizer state (fp32 master + moments) and flat parameters per bucket, so AdamW is one launch per bucket.
+        #      The order of these allocations is kept as it was: where the buffers come to lie moves the full-size step by
+        #      about 1 % (profiles/trainer_refactor_step_time.log).  Sharded, the parameters go first: the master is taken
+        #      from this rank's shard of the flat parameters, so no full-length fp32 temporary is made, which at full size
+        #      would be the replicated state that mode avoids ----
+        order = layers + self.buckets[:1]
         if self._sharded:
-            self._init_sharded_state(small)
-            return
-        # ---- optimizer state (fp32 master + moments), flat per bucket so AdamW is one launch per bucket ----
-        def flat_params(names):
-            return torch.cat([self.params[k].detach().reshape(-1).to(F32) for k in names])
-        self.master_layers = [flat_params(names) for names in self.layer_names]
-        self.master_small = flat_params(small)
-        self.small_names = small
-        z = lambda t: torch.zeros_like(t)
-        self.m_layers = [z(t) for t in self.master_layers]
-        self.v_layers = [z(t) for t in self.master_layers]
-        self.m_small, self.v_small = z(self.master_small), z(self.master_small)
-        # model parameters become views of flat bf16 buffers so the optimizer writes them in one launch
-        self.param_layers = []
-        for names in self.layer_names:
-            flat = torch.cat([self.params[k].detach().reshape(-1) for k in names]).contiguous()
-            o = 0
-            for k in names:
-                sz = self.params[k].numel()
-                self.params[k].data = flat[o:o + sz].view(self.params[k].shape)
-                o += sz
-            self.param_layers.append(flat)
-        flat = torch.cat([self.params[k].detach().reshape(-1) for k in small]).contiguous()
-        o = 0
-        for k in small:
-            sz = self.params[k].numel()
-            self.params[k].data = flat[o:o + sz].view(self.params[k].shape)
-            o += sz
-        self.param_small = flat
+            self._flatten_params(order)
+        for b in order:
+            b.master = (self._shard(b.param).to(F32, copy=True) if self._sharded else
+                        torch.cat([self.params[k].detach().reshape(-1).to(F32) for k in b.names]))
+        for kind in ("m", "v"):
+            for b in layers:
+                setattr(b, kind, torch.zeros_like(b.master))
+        self.buckets[0].m, self.buckets[0].v = (torch.zeros_like(self.buckets[0].master) for _ in range(2))
+        if not self._sharded:
+            self._flatten_params(order)
         bump_weight_generation(model)     # storage re-pointed; from here on the optimizer writes it through raw pointers
         self._init_scalars()
         self._init_ema()
+        if self._sharded:
+            self._partials = torch.zeros(self.world, dtype=F32, device=self.dev)   # every rank's sum of squares, rank order
+        # the names the records' tensors go by (bench.py, scripts/, tests): made once, the tensors are never rebound
+        small, layers = self.buckets[0], self.buckets[1:]
+        self.small_bucket, self.param_small, self.master_small = small.grad, small.param, small.master
+        self.m_small, self.v_small, self.ema_small, self._small_numel = small.m, small.v, small.ema, small.numel
+        self.layer_buckets, self.param_layers = [b.grad for b in layers], [b.param for b in layers]
+        self.master_layers, self.m_layers, self.v_layers = ([getattr(b, k) for b in layers] for k in ("master", "m", "v"))
+        self.ema_layers = [b.ema for b in layers] if self.use_ema else None
+        self._bucket_numel = [b.numel for b in layers]       # unpadded lengths of the layer buckets: the checkpoint layout
+
+    def _flatten(self, tensors, dtype, fill: bool):
+        """One flat buffer, zero-padded to the shard partition when sharded, that holds `tensors` end to end (their values
+        when `fill`, else zeros), and the views of it in their shapes."""
+        flat = torch.zeros(self._padded(sum(t.numel() for t in tensors)), dtype=dtype, device=self.dev)
+        views, o = [], 0
+        for t in tensors:
+            views.append(flat[o:o + t.numel()].view(t.shape))
+            if fill:
+                views[-1].copy_(t.detach())
+            o += t.numel()
+        return flat, views
+
+    def _make_bucket(self, key, names, grad_dtype) -> _Bucket:
+        """The record of one bucket and its flat gradient buffer, of which the gradients of `names` become views: the
+        exchange and the clip's sum of squares are one launch per bucket."""
+        ps = [self.params[k] for k in names]
+        b = _Bucket(key, names, sum(p.numel() for p in ps))
+        b.grad, views = self._flatten(ps, grad_dtype, fill=False)
+        self.grads.update(zip(names, views))
+        return b
+
+    def _flatten_params(self, buckets):
+        """The model's parameters become views of one flat buffer per bucket, which the optimizer writes in one launch."""
+        for b in buckets:
+            ps = [self.params[k] for k in b.names]
+            b.param, views = self._flatten(ps, ps[0].dtype, fill=True)
+            for p, v in zip(ps, views):
+                p.data = v
 
     # ---- sequence parallelism ------------------------------------------------------------------------------------------
     def _sp_state(self, flag, group, lora_rank):
@@ -442,27 +464,10 @@ class Stage1Trainer:
                 self._lora_g.setdefault((i, mod), {})[ab] = gr
                 self.grads[name] = unpad(gr)
         if train:
+            b = _Bucket("lora", list(self.lora), o)
+            b.grad, b.param, b.master, b.m, b.v = self.lora_bucket, self.lora_param, self.lora_master, self.lora_m, self.lora_v
+            self.buckets = [b]
             self._init_scalars()
-
-    def _lora_optimizer_step(self, lr, b1, b2, micro_batches=1):
-        """sumsq, clip coefficient and AdamW over the one adapter bucket (the caller has advanced the step counter)."""
-        self.sumsq.zero_()
-        T.sumsq(self.lora_bucket, self.sumsq)
-        w = float(self.world * micro_batches)
-        T.clip_coef(self.sumsq, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w)
-        if not self.overlap_optimizer:
-            T.adamw_step(self.lora_master, self.lora_param, self.lora_bucket, self.lora_m, self.lora_v, lr, b1, b2, self.eps,
-                         self.wd, self.step_count, self.coef)
-            return
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream())
-        self._opt_stream.wait_event(ready)
-        with torch.cuda.stream(self._opt_stream):
-            T.adamw_step(self.lora_master, self.lora_param, self.lora_bucket, self.lora_m, self.lora_v, lr, b1, b2, self.eps,
-                         self.wd, self.step_count, self.coef)
-            ev = torch.cuda.Event()
-            ev.record(self._opt_stream)
-        self._opt_events = (ev, [ev] * self.cfg.num_hidden_layers)
 
     def _merge_into(self, model, sign_scale=None):
         """W <- bf16(float(W) + s B A) on every adapted projection of `model`, through lora_up_add (Y = W, U = B, S = A)."""
@@ -497,8 +502,8 @@ class Stage1Trainer:
     def _init_ema(self):
         """update_ema(ema, model, decay=0) (train...py:288-290): the EMA starts as a copy of the fp32 master weights."""
         if self.use_ema:
-            self.ema_layers = [t.clone() for t in self.master_layers]
-            self.ema_small = self.master_small.clone()
+            for b in self.buckets[1:] + self.buckets[:1]:      # allocation order kept, like the rest of the state (__init__)
+                b.ema = b.master.clone()
 
     def _adamw(self, master, param, grad, m_, v_, ema, lr, b1, b2):
         """One AdamW launch over a flat bucket; with an EMA buffer the launch that also moves it (no second pass)."""
@@ -519,18 +524,16 @@ class Stage1Trainer:
         return 0 if self._micro == 0 else 1
 
     def _accumulators(self):
+        """Allocates every bucket's fp32 accumulator on first use; `_acc` is (small | lora, [layer 0 .. nl-1]) of them."""
         if self._acc is None:
-            z = lambda t: torch.empty(t.numel(), dtype=F32, device=self.dev)
-            if self.lora_rank is not None:
-                self._acc = (z(self.lora_bucket), [])
-            else:
-                self._acc = (z(self.small_bucket), [z(b) for b in self.layer_buckets])
+            for b in self.buckets:
+                b.acc = torch.empty(b.grad.numel(), dtype=F32, device=self.dev)
+            self._acc = (self.buckets[0].acc, [b.acc for b in self.buckets[1:]])
         return self._acc
 
     def _init_scalars(self):
         self.sumsq = torch.zeros(1, dtype=F32, device=self.dev)
         self.coef = torch.ones(1, dtype=F32, device=self.dev)
-
         self.grad_norm = torch.zeros(1, dtype=F32, device=self.dev)
 
     # ---- dp_sharding="optimizer" -----------------------------------------------------------------------------------
@@ -543,34 +546,6 @@ class Stage1Trainer:
             return flat
         s = flat.numel() // self.world
         return flat[self.rank * s:(self.rank + 1) * s]
-
-    def _init_sharded_state(self, small):
-        """Parameters become views into the front of zero-padded flat bf16 buckets (padded like the gradient buckets);
-        fp32 master weights and moments exist for this rank's shard of every bucket only, the master shard taken from the
-        parameter shard.  No full-length fp32 temporary: at full size it would be the replicated state this mode avoids."""
-        def flat_params(names):
-            n = sum(self.params[k].numel() for k in names)
-            flat = torch.zeros(self._padded(n), dtype=self.params[names[0]].dtype, device=self.dev)
-            o = 0
-            for k in names:
-                sz = self.params[k].numel()
-                flat[o:o + sz].copy_(self.params[k].detach().reshape(-1))
-                self.params[k].data = flat[o:o + sz].view(self.params[k].shape)
-                o += sz
-            return flat
-        self.param_layers = [flat_params(names) for names in self.layer_names]
-        self.param_small = flat_params(small)
-        self.small_names = small
-        self.master_layers = [self._shard(b).to(F32) for b in self.param_layers]
-        self.master_small = self._shard(self.param_small).to(F32)
-        z = lambda t: torch.zeros_like(t)
-        self.m_layers = [z(t) for t in self.master_layers]
-        self.v_layers = [z(t) for t in self.master_layers]
-        self.m_small, self.v_small = z(self.master_small), z(self.master_small)
-        bump_weight_generation(self.model)
-        self._init_scalars()
-        self._init_ema()
-        self._partials = torch.zeros(self.world, dtype=F32, device=self.dev)   # every rank's sum of squares, rank order
 
     def _reduce(self, bucket):
         """Asynchronous gradient exchange of one flat bucket: all-reduce (replicated), or a reduce-scatter whose sum lands in
@@ -655,278 +630,364 @@ class Stage1Trainer:
         call (see __init__)."""
         if update:
             self._refuse_inside_ema_weights("step(update=True)")
-        m, cfg = self.model, self.cfg
-        sp = self._sp
-        if sp is not None and self.check_sp_inputs:
+        if self._sp is not None and self.check_sp_inputs:
             self._check_sp_batch(batch, x1, t)
-        prep = self._prepare(batch)
-        # the previous step's update may still be running on its own stream, its all-gathers (sharded) still in flight
-        self._await_params(-1)               # embeddings, heads, final norm: read from the start
-        B, L, M, H, I = prep["B"], prep["L"], prep["B"] * prep["L"], cfg.hidden_size, cfg.intermediate_size
-        nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        nl = cfg.num_hidden_layers
-        nf, C, h, w = x1.shape
-        ntok = prep["ntok"]
-        Tn = nf * ntok
-        x1 = x1.to(self.dev, F32).contiguous(); x0 = x0.to(self.dev, F32).contiguous()
-        t = t.to(self.dev, F32).contiguous()
-        # ---------------- forward ----------------
-        xt = T.lerp_frames(x1, x0, t, self._buf("xt", (nf, C, h, w)))
-        cl = None
-        if clean is not None and clean.shape[0] > 0:
-            cl = T.lerp_frames(clean.to(self.dev, F32).contiguous(), x0_in.to(self.dev, F32).contiguous(),
-                               t_in.to(self.dev, F32).contiguous(), self._buf("cl", tuple(clean.shape)))
-        # sequence parallelism: this rank runs rows [r0, r1) of the one packed sequence (Ms of the M rows) through the
-        # row-local work and its nq / P heads (Wl fused q|k|v columns, dc context columns) through attention over all rows
-        Ms, rope = M, prep["rope"]
-        if sp is not None:
-            P = sp["P"]
-            shares, _ = sp_shares(M, P)
-            sizes = [e_ - a_ for a_, e_ in shares]
-            r0, r1 = shares[sp["r"]]
-            Ms, Wl, dc = r1 - r0, (nq + 2 * nk) // P * hd, nq // P * hd
-            rope = tuple(t_.view(-1, hd // 2)[r0:r1] for t_ in prep["rope"])
-        hbuf = self._buf("h", (nl + 1, Ms, H))         # layer inputs (h[l]) and the last output
-        # the sequence assembly is cheap and runs on all rows on every rank; the share is a copy of its rows
-        seq = hbuf[0] if sp is None else self._buf("seq_all", (M, H))
-        ops.embed_gather(prep["ids"], m.llm.embed_tokens.weight, out=seq.view(B, L, H))
-        pos = m.pos_embed[0]
-        if cl is not None:
-            ops.patch_embed(cl, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, pos, prep["c_rows"], seq,
-                            m.pos_embed_max_size)
-        sin = ops.timestep_sinusoid(t, m.time_token.freqs(self.dev))
-        tt, te, ada = m.time_token.mlp, m.t_embedder.mlp, m.final_layer.adaLN_modulation[1]
-        tt_pre = ops.linear_small(sin, tt[0].weight, tt[0].bias)
-        tt_act = T.act_fwd(tt_pre, ops.ACT_SILU)
-        ops.linear_small(tt_act, tt[2].weight, tt[2].bias, out=seq, out_row=prep["t_rows"], ldo=H)
-        ops.patch_embed(xt, m.x_embedder.proj.weight, m.x_embedder.proj.bias, pos, prep["x_rows"], seq,
-                        m.pos_embed_max_size)
-        if sp is not None:
-            hbuf[0].copy_(seq[r0:r1])
-        # saved activations: every layer's (normal) or ONE layer's worth, recomputed per layer in the backward (checkpointing)
-        ck = self.gradient_checkpointing
-        ns = 1 if ck else nl
-        n1 = self._buf("n1", (ns, Ms, H))
-        ctx = self._buf("ctx", (ns, Ms, nq * hd)); h2 = self._buf("h2", (ns, Ms, H)); n2 = self._buf("n2", (ns, Ms, H))
-        gu = self._buf("gu", (ns, Ms, 2 * I)); act = self._buf("act", (ns, Ms, I))
-        if sp is None:
-            qkv = self._buf("qkv", (ns, M, (nq + 2 * nk) * hd))
-            lse = self._buf("lse", (ns, B, nq, L), F32)
-        else:
-            # kept per layer: the fused q|k|v rows of EVERY rank for this rank's heads, their context and lse; the share's
-            # own q|k|v rows of all heads ("qkv") and the exchange buffers are transient
-            qkv = self._buf("qkv", (Ms, (nq + 2 * nk) * hd))
-            qkv_h = self._buf("qkv_heads", (ns, M, Wl)); ctx_h = self._buf("ctx_heads", (ns, M, dc))
-            lse = self._buf("lse", (ns, 1, nq // P, M), F32)
-            send = self._buf("sp_send", (P, Ms, Wl)); ctx_recv = self._buf("sp_ctx_recv", (P, Ms, dc))
-            by_sender = [[n * Wl] * P for n in sizes]                     # every rank sends its rows to every rank
-            by_owner = [[n * dc for n in sizes] for _ in range(P)]        # every rank sends each rank that rank's rows
-        sv = lambda li: 0 if ck else li
-        lora = self.lora_rank is not None
-        lq, lo = lora and "qkv_proj" in self.lora_targets, lora and "o_proj" in self.lora_targets
-        if lora:        # u = x A^T of both adapted projections, saved for the backward like the other activations
-            rp, ls = self.lora_rp, self.lora_scale
-            u_q = self._buf("u_q", (ns, M, rp)); u_o = self._buf("u_o", (ns, M, rp))
-
-        def layer_forward(li, with_output=True):
-            layer = m.llm.layers[li]
-            at, mlp, k = layer.self_attn, layer.mlp, sv(li)
-            self._await_params(li)           # this layer's parameters are updated (and gathered)
-            ops.rmsnorm(hbuf[li], layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=n1[k])
-            if lq:      # plain base GEMM, then y += s (x A^T) B^T and the rotation in one pass over y
-                aq = self._lora_w[(li, "qkv_proj")]
-                ops.linear(n1[k], at.qkv_proj.weight, out=qkv[k])
-                LO.lora_down(n1[k], aq["A"], rp, out=u_q[k])
-                LO.lora_up_add(qkv[k], u_q[k], aq["B"], alpha=ls, rope=(prep["rope"][0], prep["rope"][1], nq, nk, hd))
-            elif sp is None:
-                ops.linear_qkv_rope(n1[k], at.qkv_proj.weight, prep["rope"][0], prep["rope"][1], nq, nk, hd, out=qkv[k])
-            if sp is None:
-                T.attention_qkv_train(qkv[k].view(B, L, -1), prep["pm"], nq, nk, hd, ctx[k].view(B, L, -1), lse[k])
-            else:       # engine.StaticDenoiser._sp_attention with the training forward's kernel
-                ops.linear_qkv_rope(n1[k], at.qkv_proj.weight, rope[0], rope[1], nq, nk, hd, out=qkv)
-                ops.sp_pack_qkv(qkv, P, nq, nk, hd, out=send)
-                SPM.exchange_split(send, qkv_h[k], by_sender, sp["group"])
-                T.attention_qkv_train(qkv_h[k].view(1, M, Wl), prep["pm"], nq // P, nk // P, hd, ctx_h[k].view(1, M, dc),
-                                      lse[k])
-                SPM.exchange_split(ctx_h[k], ctx_recv, by_owner, sp["group"])
-                ops.sp_unpack_ctx(ctx_recv, P, out=ctx[k])
-            ops.linear(ctx[k], at.o_proj.weight, residual=hbuf[li], out=h2[k])
-            if lo:
-                ao = self._lora_w[(li, "o_proj")]
-                LO.lora_down(ctx[k], ao["A"], rp, out=u_o[k])
-                LO.lora_up_add(h2[k], u_o[k], ao["B"], alpha=ls)
-            ops.rmsnorm(h2[k], layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon,
-                        out=n2[k])
-            # gate_up_proj + act(gate) * up in one kernel that also keeps the bf16 [gate | up] for the backward: bit for bit
-            # ops.linear(n2, W) followed by T.silu_mul_fwd (tests/test_train_gpu.py), without the (M, 2I) round trip
-            ops.gated_mlp_act(n2[k], mlp.gate_up_proj.weight, mlp.act, out=act[k], gate_up_out=gu[k])
-            if with_output:
-                ops.linear(act[k], mlp.down_proj.weight, residual=h2[k], out=hbuf[li + 1])
-
-        for li in range(nl):
-            layer_forward(li)
-        if sp is None:
-            nrm = ops.rmsnorm(hbuf[nl], m.llm.norm.weight, m.llm.norm.variance_epsilon, out=self._buf("nrm", (M, H)))
-        else:
-            # final norm on the share, then ONE exchange leaves the normed rows of every rank on every rank (Gather.forward,
-            # LVM/utils.py:148-161; shares padded to the largest): the heads below, the loss and their backward run
-            # replicated, so the loss vector is the same bits on every rank
-            pad = self._buf("nrm_pad", (max(sizes), H))
-            ops.rmsnorm(hbuf[nl], m.llm.norm.weight, m.llm.norm.variance_epsilon, out=pad[:Ms])
-            every = SPM.all_gather_flat(pad, sp["group"], out=self._buf("nrm_every", (P, max(sizes) * H)))
-            nrm = self._buf("nrm", (M, H))
-            for i, (a_, e_) in enumerate(shares):
-                nrm[a_:e_].copy_(every[i].view(-1, H)[:e_ - a_])
-        te_pre = ops.linear_small(sin, te[0].weight, te[0].bias)
-        te_act = T.act_fwd(te_pre, ops.ACT_SILU)
-        temb = ops.linear_small(te_act, te[2].weight, te[2].bias)
-        st = T.act_fwd(temb, ops.ACT_SILU)
-        mod = ops.linear_small(st, ada.weight, ada.bias)
-        v = self._buf("v", (Tn, H)); xhat = self._buf("xhat", (Tn, H), F32); rstd = self._buf("rstd", (Tn,), F32)
-        T.ln_mod_fwd(nrm, prep["x_rows"], mod, v, xhat, rstd, ntok)
-        fl = m.final_layer.linear
-        y16 = ops.linear(v, fl.weight, bias=fl.bias)                       # (Tn, 16)
-        p2 = m.patch_size
-        pred = y16.view(nf, h // p2, w // p2, p2, p2, C).permute(0, 5, 1, 3, 2, 4).reshape(nf, C, h, w).contiguous()
-        loss = torch.empty(nf, dtype=F32, device=self.dev)
-        dpred = self._buf("dpred", (nf, C, h, w))
-        head = None
-        if input_output_return:
-            # LVM/model.py:832-841 + loss.py:220-225: the input_final_layer head predicts the CLEAN condition latents from the
-            # last hidden state of their rows; its per-frame MSE terms are appended to the loss vector before .mean()
-            if cl is None:
-                raise VgptError("Stage1Trainer.step: input_output_return needs condition frames")
-            head = m.input_final_layer           # AttributeError without init_input_final_layer(), as in the reference
-            nfc = clean.shape[0]
-            vin = T.gather_rows(nrm, prep["c_rows"], ntok)                   # (nfc * ntok, H)
-            yin = ops.linear(vin, head.weight, bias=head.bias)
-            pred_in = yin.view(nfc, h // p2, w // p2, p2, p2, C).permute(0, 5, 1, 3, 2, 4).reshape(nfc, C, h, w).contiguous()
-            loss_in = torch.empty(nfc, dtype=F32, device=self.dev)
-            dpred_in = self._buf("dpred_in", (nfc, C, h, w))
-            T.mse_frames(pred_in, clean.to(self.dev, F32).contiguous(), loss_in, dpred_in, n_mean=nf + nfc)
-            T.mse_frames(pred, x1, loss, dpred, n_mean=nf + nfc)
-            loss = torch.cat([loss, loss_in])
-            self.last = dict(pred=pred, loss=loss, xt=xt, pred_in=pred_in)
-        else:
-            T.mse_frames(pred, x1, loss, dpred)
-            self.last = dict(pred=pred, loss=loss, xt=xt)
+        f = self._begin_step(batch, x1, x0, t, clean, x0_in, t_in)
+        self._assemble_sequence(f)
+        self._decoder_forward(f)
+        loss = self._heads_and_loss(f, input_output_return)
         if self.forward_only or not backward:
             if update:
                 raise VgptError("Stage1Trainer.step: an optimizer step needs the backward pass")
             return loss
         acc_mode = self._accum_mode(update)
-        exchange = acc_mode in (None, 2)     # micro-steps before the last issue no collective
-        if lora:
-            self._lora_backward(locals())
-            if update:
-                self._finish_micro_step(acc_mode)
+        self._exchange(self._backward(f, acc_mode), acc_mode)
+        if update:
+            self._finish_micro_step(acc_mode)
+        return loss
+
+    # ---- the phases of step(), in order.  `f` is the record the forward phases fill and the backward reads: shapes, the
+    #      saved activation buffers, the head intermediates and, under sequence parallelism, this rank's share ----
+    def _begin_step(self, batch, x1, x0, t, clean, x0_in, t_in):
+        """Prepare: row layout of the batch, shapes, the noised latents, and the share of a sequence-parallel rank."""
+        cfg, sp = self.cfg, self._sp
+        prep = self._prepare(batch)
+        # the previous step's update may still be running on its own stream, its all-gathers (sharded) still in flight
+        self._await_params(-1)               # embeddings, heads, final norm: read from the start
+        f = SimpleNamespace(prep=prep, sp=sp, B=prep["B"], L=prep["L"], M=prep["B"] * prep["L"], H=cfg.hidden_size,
+                            I=cfg.intermediate_size, nq=cfg.num_attention_heads, nk=cfg.num_key_value_heads, hd=cfg.head_dim,
+                            nl=cfg.num_hidden_layers, ntok=prep["ntok"], ck=self.gradient_checkpointing, clean=clean)
+        f.nf, f.C, f.h, f.w = x1.shape
+        f.x1 = x1.to(self.dev, F32).contiguous(); x0 = x0.to(self.dev, F32).contiguous()
+        f.t = t.to(self.dev, F32).contiguous()
+        f.xt = T.lerp_frames(f.x1, x0, f.t, self._buf("xt", tuple(x1.shape)))
+        f.cl = None
+        if clean is not None and clean.shape[0] > 0:
+            f.cl = T.lerp_frames(clean.to(self.dev, F32).contiguous(), x0_in.to(self.dev, F32).contiguous(),
+                                 t_in.to(self.dev, F32).contiguous(), self._buf("cl", tuple(clean.shape)))
+        # sequence parallelism: this rank runs rows [r0, r1) of the one packed sequence (Ms of the M rows) through the
+        # row-local work and its nq / P heads (Wl fused q|k|v columns, dc context columns) through attention over all rows
+        f.r0, f.r1, f.Ms, f.rope = 0, f.M, f.M, prep["rope"]
+        if sp is not None:
+            P = sp["P"]
+            f.shares, _ = sp_shares(f.M, P)
+            f.sizes = sizes = [e_ - a_ for a_, e_ in f.shares]
+            f.r0, f.r1 = f.shares[sp["r"]]
+            f.Ms, f.Wl, f.dc = f.r1 - f.r0, (f.nq + 2 * f.nk) // P * f.hd, f.nq // P * f.hd
+            f.rope = tuple(t_.view(-1, f.hd // 2)[f.r0:f.r1] for t_ in prep["rope"])
+            # split lists of the four exchanges per layer: rows go to the ranks that own the heads and back
+            f.by_sender = [[n * f.Wl] * P for n in sizes]                 # every rank sends its rows to every rank
+            f.by_owner = [[n * f.dc for n in sizes] for _ in range(P)]    # every rank sends each rank that rank's rows
+            f.ctx_by_sender = [[n * f.dc] * P for n in sizes]
+            f.qkv_by_owner = [[n * f.Wl for n in sizes] for _ in range(P)]
+        f.lq = self.lora_rank is not None and "qkv_proj" in self.lora_targets
+        f.lo = self.lora_rank is not None and "o_proj" in self.lora_targets
+        return f
+
+    def _assemble_sequence(self, f):
+        """The decoder's input rows: token embeddings, condition and noised patches, the time token.  Cheap, so it runs on
+        all rows on every rank; a sequence-parallel share is a copy of its rows."""
+        m, prep, H = self.model, f.prep, f.H
+        f.hbuf = self._buf("h", (f.nl + 1, f.Ms, H))         # layer inputs (h[l]) and the last output
+        seq = f.hbuf[0] if f.sp is None else self._buf("seq_all", (f.M, H))
+        ops.embed_gather(prep["ids"], m.llm.embed_tokens.weight, out=seq.view(f.B, f.L, H))
+        pos = m.pos_embed[0]
+        if f.cl is not None:
+            ops.patch_embed(f.cl, m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias, pos, prep["c_rows"], seq,
+                            m.pos_embed_max_size)
+        f.sin = ops.timestep_sinusoid(f.t, m.time_token.freqs(self.dev))
+        tt = m.time_token.mlp
+        f.tt_pre = ops.linear_small(f.sin, tt[0].weight, tt[0].bias)
+        f.tt_act = T.act_fwd(f.tt_pre, ops.ACT_SILU)
+        ops.linear_small(f.tt_act, tt[2].weight, tt[2].bias, out=seq, out_row=prep["t_rows"], ldo=H)
+        ops.patch_embed(f.xt, m.x_embedder.proj.weight, m.x_embedder.proj.bias, pos, prep["x_rows"], seq,
+                        m.pos_embed_max_size)
+        if f.sp is not None:
+            f.hbuf[0].copy_(seq[f.r0:f.r1])
+
+    def _decoder_forward(self, f):
+        """Every decoder layer, keeping what the backward reads: every layer's activations (normal) or ONE layer's worth,
+        recomputed per layer in the backward (checkpointing)."""
+        B, L, M, Ms, H, I, nq, nk, hd = f.B, f.L, f.M, f.Ms, f.H, f.I, f.nq, f.nk, f.hd
+        ns = 1 if f.ck else f.nl
+        f.n1 = self._buf("n1", (ns, Ms, H))
+        f.ctx = self._buf("ctx", (ns, Ms, nq * hd)); f.h2 = self._buf("h2", (ns, Ms, H)); f.n2 = self._buf("n2", (ns, Ms, H))
+        f.gu = self._buf("gu", (ns, Ms, 2 * I)); f.act = self._buf("act", (ns, Ms, I))
+        if f.sp is None:
+            f.qkv = self._buf("qkv", (ns, M, (nq + 2 * nk) * hd))
+            f.lse = self._buf("lse", (ns, B, nq, L), F32)
+        else:
+            # kept per layer: the fused q|k|v rows of EVERY rank for this rank's heads, their context and lse; the share's
+            # own q|k|v rows of all heads ("qkv") and the exchange buffers are transient
+            P = f.sp["P"]
+            f.qkv = self._buf("qkv", (Ms, (nq + 2 * nk) * hd))
+            f.qkv_h = self._buf("qkv_heads", (ns, M, f.Wl)); f.ctx_h = self._buf("ctx_heads", (ns, M, f.dc))
+            f.lse = self._buf("lse", (ns, 1, nq // P, M), F32)
+            f.send = self._buf("sp_send", (P, Ms, f.Wl)); f.ctx_recv = self._buf("sp_ctx_recv", (P, Ms, f.dc))
+        if self.lora_rank is not None:      # u = x A^T of both adapted projections, saved like the other activations
+            f.u_q = self._buf("u_q", (ns, M, self.lora_rp)); f.u_o = self._buf("u_o", (ns, M, self.lora_rp))
+        for li in range(f.nl):
+            self._layer_forward(f, li)
+
+    def _layer_forward(self, f, li, with_output=True):
+        """Decoder layer li; the checkpointing backward calls it again with with_output=False."""
+        layer = self.model.llm.layers[li]
+        at, mlp, k = layer.self_attn, layer.mlp, 0 if f.ck else li
+        self._await_params(li)           # this layer's parameters are updated (and gathered)
+        ops.rmsnorm(f.hbuf[li], layer.input_layernorm.weight, layer.input_layernorm.variance_epsilon, out=f.n1[k])
+        self._attention_forward(f, li, k)
+        ops.linear(f.ctx[k], at.o_proj.weight, residual=f.hbuf[li], out=f.h2[k])
+        if f.lo:
+            ao = self._lora_w[(li, "o_proj")]
+            LO.lora_down(f.ctx[k], ao["A"], self.lora_rp, out=f.u_o[k])
+            LO.lora_up_add(f.h2[k], f.u_o[k], ao["B"], alpha=self.lora_scale)
+        ops.rmsnorm(f.h2[k], layer.post_attention_layernorm.weight, layer.post_attention_layernorm.variance_epsilon,
+                    out=f.n2[k])
+        # gate_up_proj + act(gate) * up in one kernel that also keeps the bf16 [gate | up] for the backward: bit for bit
+        # ops.linear(n2, W) followed by T.silu_mul_fwd (tests/test_train_gpu.py), without the (M, 2I) round trip
+        ops.gated_mlp_act(f.n2[k], mlp.gate_up_proj.weight, mlp.act, out=f.act[k], gate_up_out=f.gu[k])
+        if with_output:
+            ops.linear(f.act[k], mlp.down_proj.weight, residual=f.h2[k], out=f.hbuf[li + 1])
+
+    def _attention_forward(self, f, li, k):
+        """n1[k] -> ctx[k]: qkv_proj + RoPE, (pack, exchange,) attention (, exchange, unpack)."""
+        at, sp, pm = self.model.llm.layers[li].self_attn, f.sp, f.prep["pm"]
+        B, L, M, nq, nk, hd = f.B, f.L, f.M, f.nq, f.nk, f.hd
+        qkv = f.qkv[k] if sp is None else f.qkv
+        if f.lq:        # plain base GEMM, then y += s (x A^T) B^T and the rotation in one pass over y
+            aq = self._lora_w[(li, "qkv_proj")]
+            ops.linear(f.n1[k], at.qkv_proj.weight, out=qkv)
+            LO.lora_down(f.n1[k], aq["A"], self.lora_rp, out=f.u_q[k])
+            LO.lora_up_add(qkv, f.u_q[k], aq["B"], alpha=self.lora_scale, rope=(f.rope[0], f.rope[1], nq, nk, hd))
+        else:
+            ops.linear_qkv_rope(f.n1[k], at.qkv_proj.weight, f.rope[0], f.rope[1], nq, nk, hd, out=qkv)
+        if sp is None:
+            T.attention_qkv_train(qkv.view(B, L, -1), pm, nq, nk, hd, f.ctx[k].view(B, L, -1), f.lse[k])
+            return
+        # engine.StaticDenoiser._sp_attention with the training forward's kernel
+        P = sp["P"]
+        ops.sp_pack_qkv(qkv, P, nq, nk, hd, out=f.send)
+        SPM.exchange_split(f.send, f.qkv_h[k], f.by_sender, sp["group"])
+        T.attention_qkv_train(f.qkv_h[k].view(1, M, f.Wl), pm, nq // P, nk // P, hd, f.ctx_h[k].view(1, M, f.dc), f.lse[k])
+        SPM.exchange_split(f.ctx_h[k], f.ctx_recv, f.by_owner, sp["group"])
+        ops.sp_unpack_ctx(f.ctx_recv, P, out=f.ctx[k])
+
+    def _attention_backward(self, f, k, dctx, dqkv):
+        """_attention_forward's mirror: d(ctx[k]) -> d(qkv_proj's output), rotated back."""
+        sp, pm = f.sp, f.prep["pm"]
+        B, L, M, nq, nk, hd = f.B, f.L, f.M, f.nq, f.nk, f.hd
+        if sp is None:
+            T.attention_qkv_bwd(f.qkv[k].view(B, L, -1), f.ctx[k].view(B, L, -1), dctx.view(B, L, -1), f.lse[k], f.delta,
+                                dqkv.view(B, L, -1), pm, nq, nk, hd)
+            ops.rope_qk_inplace(dqkv, f.rope[0], f.nsin, nq, nk, hd)                     # inverse rotation
+            return
+        # the forward's two exchanges, mirrored: d(ctx) of my rows goes to the ranks that own the heads, d(qkv) of my heads
+        # goes back to the ranks that own the rows, and is rotated back on its way into row order
+        P = sp["P"]
+        ops.sp_pack_ctx(dctx, P, out=f.dctx_send)
+        SPM.exchange_split(f.dctx_send, f.dctx_h, f.ctx_by_sender, sp["group"])
+        T.attention_qkv_bwd(f.qkv_h[k].view(1, M, f.Wl), f.ctx_h[k].view(1, M, f.dc), f.dctx_h.view(1, M, f.dc), f.lse[k],
+                            f.delta, f.dqkv_h.view(1, M, f.Wl), pm, nq // P, nk // P, hd)
+        SPM.exchange_split(f.dqkv_h, f.dqkv_recv, f.qkv_by_owner, sp["group"])
+        ops.sp_unpack_qkv_rope(f.dqkv_recv, P, nq, nk, hd, f.rope[0], f.nsin, out=dqkv)
+
+    def _attention_backward_buffers(self, f):
+        f.nsin = self._neg_sin(f.prep)
+        if f.sp is None:
+            f.delta = self._buf("delta", (f.B, f.nq, f.L), F32)
+            return
+        P, M, Ms = f.sp["P"], f.M, f.Ms
+        f.delta = self._buf("delta", (1, f.nq // P, M), F32)
+        f.nsin = f.nsin.view(-1, f.hd // 2)[f.r0:f.r1]
+        f.dctx_send = self._buf("sp_dctx_send", (P, Ms, f.dc)); f.dctx_h = self._buf("dctx_heads", (M, f.dc))
+        f.dqkv_h = self._buf("dqkv_heads", (M, f.Wl)); f.dqkv_recv = self._buf("sp_dqkv_recv", (P, Ms, f.Wl))
+
+    def _heads_and_loss(self, f, input_output_return):
+        """Final norm, the adaLN-modulated output head (and the input_final_layer head), the per-frame MSE and d(pred)."""
+        m, prep, sp = self.model, f.prep, f.sp
+        M, H, nl, nf, C, h, w, ntok = f.M, f.H, f.nl, f.nf, f.C, f.h, f.w, f.ntok
+        if sp is None:
+            nrm = ops.rmsnorm(f.hbuf[nl], m.llm.norm.weight, m.llm.norm.variance_epsilon, out=self._buf("nrm", (M, H)))
+        else:
+            # final norm on the share, then ONE exchange leaves the normed rows of every rank on every rank (Gather.forward,
+            # LVM/utils.py:148-161; shares padded to the largest): the heads below, the loss and their backward run
+            # replicated, so the loss vector is the same bits on every rank
+            pad = self._buf("nrm_pad", (max(f.sizes), H))
+            ops.rmsnorm(f.hbuf[nl], m.llm.norm.weight, m.llm.norm.variance_epsilon, out=pad[:f.Ms])
+            every = SPM.all_gather_flat(pad, sp["group"], out=self._buf("nrm_every", (sp["P"], max(f.sizes) * H)))
+            nrm = self._buf("nrm", (M, H))
+            for i, (a_, e_) in enumerate(f.shares):
+                nrm[a_:e_].copy_(every[i].view(-1, H)[:e_ - a_])
+        te, ada = m.t_embedder.mlp, m.final_layer.adaLN_modulation[1]
+        f.te_pre = ops.linear_small(f.sin, te[0].weight, te[0].bias)
+        f.te_act = T.act_fwd(f.te_pre, ops.ACT_SILU)
+        f.temb = ops.linear_small(f.te_act, te[2].weight, te[2].bias)
+        f.st = T.act_fwd(f.temb, ops.ACT_SILU)
+        f.mod = ops.linear_small(f.st, ada.weight, ada.bias)
+        Tn = nf * ntok
+        f.v = self._buf("v", (Tn, H)); f.xhat = self._buf("xhat", (Tn, H), F32); f.rstd = self._buf("rstd", (Tn,), F32)
+        T.ln_mod_fwd(nrm, prep["x_rows"], f.mod, f.v, f.xhat, f.rstd, ntok)
+        fl = m.final_layer.linear
+        y16 = ops.linear(f.v, fl.weight, bias=fl.bias)                     # (Tn, 16)
+        p2 = m.patch_size
+        pred = y16.view(nf, h // p2, w // p2, p2, p2, C).permute(0, 5, 1, 3, 2, 4).reshape(nf, C, h, w).contiguous()
+        loss = torch.empty(nf, dtype=F32, device=self.dev)
+        f.dpred = self._buf("dpred", (nf, C, h, w))
+        f.head = None
+        if not input_output_return:
+            T.mse_frames(pred, f.x1, loss, f.dpred)
+            self.last = dict(pred=pred, loss=loss, xt=f.xt)
             return loss
-        # ---------------- backward ----------------
-        g = self.grads
-        det = self.deterministic     # the fixed-order twins of the three reductions that add with atomics (DESIGN.md §6d)
-        self.small_bucket.zero_()
-        dy16 = T.unpatchify_bwd(dpred)                                      # (Tn, 16)
-        T.matmul(dy16, v, out=g["final_layer.linear.weight"], ta=True)     # dWf = dy16^T v
-        T.colsum(dy16, g["final_layer.linear.bias"])
+        # LVM/model.py:832-841 + loss.py:220-225: the input_final_layer head predicts the CLEAN condition latents from the
+        # last hidden state of their rows; its per-frame MSE terms are appended to the loss vector before .mean()
+        if f.cl is None:
+            raise VgptError("Stage1Trainer.step: input_output_return needs condition frames")
+        f.head = m.input_final_layer           # AttributeError without init_input_final_layer(), as in the reference
+        nfc = f.clean.shape[0]
+        f.vin = T.gather_rows(nrm, prep["c_rows"], ntok)                 # (nfc * ntok, H)
+        yin = ops.linear(f.vin, f.head.weight, bias=f.head.bias)
+        pred_in = yin.view(nfc, h // p2, w // p2, p2, p2, C).permute(0, 5, 1, 3, 2, 4).reshape(nfc, C, h, w).contiguous()
+        loss_in = torch.empty(nfc, dtype=F32, device=self.dev)
+        f.dpred_in = self._buf("dpred_in", (nfc, C, h, w))
+        T.mse_frames(pred_in, f.clean.to(self.dev, F32).contiguous(), loss_in, f.dpred_in, n_mean=nf + nfc)
+        T.mse_frames(pred, f.x1, loss, f.dpred, n_mean=nf + nfc)
+        loss = torch.cat([loss, loss_in])
+        self.last = dict(pred=pred, loss=loss, xt=f.xt, pred_in=pred_in)
+        return loss
+
+    def _backward(self, f, acc_mode):
+        """The explicit backward.  A full trainer fills every gradient; per decoder layer it accumulates (acc_mode) and
+        starts the exchange of that layer's bucket right behind its last dW, and returns the handles of those exchanges.
+        With the base frozen (LoRA) it is the same dX chain without a single dW GEMM, and per adapted projection
+        dB = s dy^T u, du = s dy B, dA = du^T x, dx += du A; nothing that only feeds frozen parameters is computed: no
+        head / adaLN / embedder / embedding gradients, no dx below layer 0's qkv_proj, and the gain gradients of the
+        frozen norms go to a scratch vector."""
+        m, prep, g, full = self.model, f.prep, self.grads, self.lora_rank is None
+        M, Ms, H, I, nq, nk, hd, nl, ntok = f.M, f.Ms, f.H, f.I, f.nq, f.nk, f.hd, f.nl, f.ntok
+        rp, ls = (None, None) if full else (self.lora_rp, self.lora_scale)
+        det = self.deterministic     # the fixed-order twins of the three reductions that add with atomics (DESIGN.md §6d);
+        #                              the discarded dgain / dmod sums of a LoRA trainer too: one rule for every path
+        exchange = acc_mode in (None, 2)     # micro-steps before the last issue no collective
+        # small bucket: zeroed for the sums below; adapter bucket: a target module left out keeps zero gradients
+        self.buckets[0].grad.zero_()
+        dy16 = T.unpatchify_bwd(f.dpred)                                    # (Tn, 16)
+        fl, ada = m.final_layer.linear, m.final_layer.adaLN_modulation[1]
+        if full:
+            T.matmul(dy16, f.v, out=g["final_layer.linear.weight"], ta=True)     # dWf = dy16^T v
+            T.colsum(dy16, g["final_layer.linear.bias"])
         dv = T.matmul(dy16, fl.weight)                                      # (Tn, H)
         dnrm = self._buf("dnrm", (M, H)); dnrm.zero_()
-        dmod = torch.zeros(nf, 2 * H, dtype=F32, device=self.dev)
-        T.ln_mod_bwd(dv, xhat, rstd, mod, prep["x_rows"], dnrm, dmod, ntok, deterministic=det)
-        if head is not None:
-            dyin = T.unpatchify_bwd(dpred_in)                                # (nfc * ntok, 16)
-            T.matmul(dyin, vin, out=g["input_final_layer.weight"], ta=True)
-            T.colsum(dyin, g["input_final_layer.bias"])
-            dnrm.index_copy_(0, prep["c_idx"], T.matmul(dyin, head.weight))  # condition rows: no other gradient reaches them here
+        if full:
+            dmod = torch.zeros(f.nf, 2 * H, dtype=F32, device=self.dev)
+            gain = g.__getitem__
+        else:
+            dmod = self._buf("dmod_scratch", (f.nf, 2 * H), F32); dmod.zero_()   # feeds adaLN only: discarded
+            dgain = self._buf("dgain_scratch", (H,), F32); dgain.zero_()         # gain gradients of the frozen norms: discarded
+            gain = lambda name: dgain
+        T.ln_mod_bwd(dv, f.xhat, f.rstd, f.mod, prep["x_rows"], dnrm, dmod, ntok, deterministic=det)
+        if f.head is not None:
+            dyin = T.unpatchify_bwd(f.dpred_in)                              # (nfc * ntok, 16)
+            if full:
+                T.matmul(dyin, f.vin, out=g["input_final_layer.weight"], ta=True)
+                T.colsum(dyin, g["input_final_layer.bias"])
+            dnrm.index_copy_(0, prep["c_idx"], T.matmul(dyin, f.head.weight))    # condition rows: no other gradient reaches them here
         dh = self._buf("dh", (Ms, H)); dh_b = self._buf("dh_b", (Ms, H))
         # sharded: every rank keeps its own rows of dnrm (Gather.backward, LVM/utils.py:163-169): no exchange
-        T.rmsnorm_bwd(hbuf[nl], m.llm.norm.weight, dnrm if sp is None else dnrm[r0:r1], dh, g["llm.norm.weight"],
+        T.rmsnorm_bwd(f.hbuf[nl], m.llm.norm.weight, dnrm if f.sp is None else dnrm[f.r0:f.r1], dh, gain("llm.norm.weight"),
                       m.llm.norm.variance_epsilon, deterministic=det)
-        # adaLN + t_embedder
-        T.matmul(dmod, st, out=g["final_layer.adaLN_modulation.1.weight"], ta=True)
-        T.colsum(dmod, g["final_layer.adaLN_modulation.1.bias"])
-        dtemb = T.act_bwd(temb, T.matmul(dmod, ada.weight), ops.ACT_SILU)
-        self._mlp_bwd("t_embedder", te, dtemb, te_act, te_pre, sin)
-        # decoder layers, last to first
-        sw = sa = sb = None   # dX / dW read their operands transposed inside the GEMM (vgpt_gemm_bf16_tr)
+        if full:        # adaLN + t_embedder
+            T.matmul(dmod, f.st, out=g["final_layer.adaLN_modulation.1.weight"], ta=True)
+            T.colsum(dmod, g["final_layer.adaLN_modulation.1.bias"])
+            dtemb = T.act_bwd(f.temb, T.matmul(dmod, ada.weight), ops.ACT_SILU)
+            self._mlp_bwd("t_embedder", m.t_embedder.mlp, dtemb, f.te_act, f.te_pre, f.sin)
+        # decoder layers, last to first; dX / dW read their operands transposed inside the GEMM (vgpt_gemm_bf16_tr): no
+        # transposed copies are passed
         dact = self._buf("dact", (Ms, I)); dgu = self._buf("dgu", (Ms, 2 * I)); dn = self._buf("dn", (Ms, H))
         dctx = self._buf("dctx", (Ms, nq * hd)); dqkv = self._buf("dqkv", (Ms, (nq + 2 * nk) * hd))
-        nsin = self._neg_sin(prep)
-        if sp is None:
-            delta = self._buf("delta", (B, nq, L), F32)
-        else:
-            delta = self._buf("delta", (1, nq // P, M), F32)
-            nsin = nsin.view(-1, hd // 2)[r0:r1]
-            dctx_send = self._buf("sp_dctx_send", (P, Ms, dc)); dctx_h = self._buf("dctx_heads", (M, dc))
-            dqkv_h = self._buf("dqkv_heads", (M, Wl)); dqkv_recv = self._buf("sp_dqkv_recv", (P, Ms, Wl))
-            ctx_by_sender = [[n * dc] * P for n in sizes]
-            qkv_by_owner = [[n * Wl for n in sizes] for _ in range(P)]
+        self._attention_backward_buffers(f)
+        if not full:
+            du = self._buf("du", (M, rp))
         handles = []
         for li in range(nl - 1, -1, -1):
             layer = m.llm.layers[li]
             at, mlp = layer.self_attn, layer.mlp
-            names = self.layer_names[li]
-            if ck:      # same kernels on the same inputs as the forward pass: the recomputed activations are bit-identical
-                layer_forward(li, with_output=False)
-            k = sv(li)
-            T.linear_dw(dh, act[k], sa, sb, g[names[3]])                               # dW_down
-            T.linear_dx(dh, mlp.down_proj.weight, sw, out=dact)
-            T.silu_mul_bwd(gu[k], dact, dgu, mlp.act)
-            T.linear_dw(dgu, n2[k], sa, sb, g[names[2]])                               # dW_gate_up
-            T.linear_dx(dgu, mlp.gate_up_proj.weight, sw, out=dn)
-            T.rmsnorm_bwd(h2[k], layer.post_attention_layernorm.weight, dn, dh_b,
-                          g[f"llm.layers.{li}.post_attention_layernorm.weight"],
+            names = self.layer_names[li] if full else None
+            if f.ck:    # same kernels on the same inputs as the forward pass: the recomputed activations are bit-identical
+                self._layer_forward(f, li, with_output=False)
+            k = 0 if f.ck else li
+            if full:
+                T.linear_dw(dh, f.act[k], None, None, g[names[3]])                      # dW_down
+            T.linear_dx(dh, mlp.down_proj.weight, None, out=dact)
+            T.silu_mul_bwd(f.gu[k], dact, dgu, mlp.act)
+            if full:
+                T.linear_dw(dgu, f.n2[k], None, None, g[names[2]])                      # dW_gate_up
+            T.linear_dx(dgu, mlp.gate_up_proj.weight, None, out=dn)
+            T.rmsnorm_bwd(f.h2[k], layer.post_attention_layernorm.weight, dn, dh_b,
+                          gain(f"llm.layers.{li}.post_attention_layernorm.weight"),
                           layer.post_attention_layernorm.variance_epsilon, dres=dh, deterministic=det)   # dh2
-            T.linear_dw(dh_b, ctx[k], sa, sb, g[names[1]])                             # dW_o
-            T.linear_dx(dh_b, at.o_proj.weight, sw, out=dctx)
-            if sp is None:
-                T.attention_qkv_bwd(qkv[k].view(B, L, -1), ctx[k].view(B, L, -1), dctx.view(B, L, -1), lse[k], delta,
-                                    dqkv.view(B, L, -1), prep["pm"], nq, nk, hd)
-                ops.rope_qk_inplace(dqkv, prep["rope"][0], nsin, nq, nk, hd)             # inverse rotation
-            else:
-                # the forward's two exchanges, mirrored: d(ctx) of my rows goes to the ranks that own the heads, d(qkv) of
-                # my heads goes back to the ranks that own the rows, and is rotated back on its way into row order
-                ops.sp_pack_ctx(dctx, P, out=dctx_send)
-                SPM.exchange_split(dctx_send, dctx_h, ctx_by_sender, sp["group"])
-                T.attention_qkv_bwd(qkv_h[k].view(1, M, Wl), ctx_h[k].view(1, M, dc), dctx_h.view(1, M, dc), lse[k], delta,
-                                    dqkv_h.view(1, M, Wl), prep["pm"], nq // P, nk // P, hd)
-                SPM.exchange_split(dqkv_h, dqkv_recv, qkv_by_owner, sp["group"])
-                ops.sp_unpack_qkv_rope(dqkv_recv, P, nq, nk, hd, rope[0], nsin, out=dqkv)
-            T.linear_dw(dqkv, n1[k], sa, sb, g[names[0]])                              # dW_qkv
-            T.linear_dx(dqkv, at.qkv_proj.weight, sw, out=dn)
-            T.rmsnorm_bwd(hbuf[li], layer.input_layernorm.weight, dn, dh,
-                          g[f"llm.layers.{li}.input_layernorm.weight"], layer.input_layernorm.variance_epsilon,
-                          dres=dh_b, deterministic=det)                                  # dh (layer input)
-            if acc_mode is not None:     # right behind this layer's last dW, where its bucket is complete
-                T.grad_accumulate(self._accumulators()[1][li], self.layer_buckets[li], acc_mode)
-            if exchange and self.world > 1 and not self.skip_allreduce and self.overlap_allreduce:
-                handles.append(self._reduce(self.layer_buckets[li]))
+            if full:
+                T.linear_dw(dh_b, f.ctx[k], None, None, g[names[1]])                    # dW_o
+            T.linear_dx(dh_b, at.o_proj.weight, None, out=dctx)
+            if f.lo:
+                ao, go = self._lora_w[(li, "o_proj")], self._lora_g[(li, "o_proj")]
+                LO.lora_grad(dh_b, f.u_o[k], go["B"], alpha=ls)                          # dB = s dy^T u
+                LO.lora_down(dh_b, ao["B"], rp, s_is_k_by_rp=True, alpha=ls, out=du)     # du = s dy B
+                LO.lora_grad(f.ctx[k], du, go["A"], transposed=True)                     # dA = du^T x
+                LO.lora_up_add(dctx, du, ao["A"], s_is_rp_by_n=True)                     # dx += du A
+            self._attention_backward(f, k, dctx, dqkv)
+            if full:
+                T.linear_dw(dqkv, f.n1[k], None, None, g[names[0]])                     # dW_qkv
+            if f.lq:
+                aq, gq = self._lora_w[(li, "qkv_proj")], self._lora_g[(li, "qkv_proj")]
+                LO.lora_grad(dqkv, f.u_q[k], gq["B"], alpha=ls)
+                LO.lora_down(dqkv, aq["B"], rp, s_is_k_by_rp=True, alpha=ls, out=du)
+                LO.lora_grad(f.n1[k], du, gq["A"], transposed=True)
+            if li == 0 and not full:
+                return handles       # everything below layer 0's qkv_proj is frozen
+            T.linear_dx(dqkv, at.qkv_proj.weight, None, out=dn)
+            if f.lq:
+                LO.lora_up_add(dn, du, aq["A"], s_is_rp_by_n=True)
+            T.rmsnorm_bwd(f.hbuf[li], layer.input_layernorm.weight, dn, dh, gain(f"llm.layers.{li}.input_layernorm.weight"),
+                          layer.input_layernorm.variance_epsilon, dres=dh_b, deterministic=det)   # dh (layer input)
+            if full:
+                b = self.buckets[1 + li]
+                if acc_mode is not None:     # right behind this layer's last dW, where its bucket is complete
+                    T.grad_accumulate(self._accumulators()[1][li], b.grad, acc_mode)
+                if exchange and self.world > 1 and not self.skip_allreduce and self.overlap_allreduce:
+                    handles.append(self._reduce(b.grad))
         # heads fed by dseq = dh (sharded: zero outside the share, so what follows yields this rank's partial gradients)
         dseq = dh
-        if sp is not None:
+        if f.sp is not None:
             dseq = self._buf("dseq", (M, H)); dseq.zero_()
-            dseq[r0:r1].copy_(dh)
-            if sp["r"] > 0:      # computed on replicated rows: they enter the sum over the ranks from SP rank 0 alone
+            dseq[f.r0:f.r1].copy_(dh)
+            if f.sp["r"] > 0:    # computed on replicated rows: they enter the sum over the ranks from SP rank 0 alone
                 for name in g:
                     if name.startswith(SP_REPLICATED):
                         g[name].zero_()
         dtt = T.gather_rows(dseq, prep["t_rows"], 1)
-        self._mlp_bwd("time_token", tt, dtt, tt_act, tt_pre, sin)
-        self._patch_bwd("x_embedder", T.gather_rows(dseq, prep["x_rows"], ntok), xt)
-        if cl is not None:
-            self._patch_bwd("input_x_embedder", T.gather_rows(dseq, prep["c_rows"], ntok), cl)
+        self._mlp_bwd("time_token", m.time_token.mlp, dtt, f.tt_act, f.tt_pre, f.sin)
+        self._patch_bwd("x_embedder", T.gather_rows(dseq, prep["x_rows"], ntok), f.xt)
+        if f.cl is not None:
+            self._patch_bwd("input_x_embedder", T.gather_rows(dseq, prep["c_rows"], ntok), f.cl)
         T.embed_bwd(prep["ids"].view(-1), prep["keep"], dseq, g["llm.embed_tokens.weight"], deterministic=det)
+        return handles
+
+    def _exchange(self, handles, acc_mode):
+        """The last bucket of the backward (the small one; LoRA: the one adapter bucket) is complete only now: accumulate
+        and exchange it, behind the layer buckets where those did not go layer by layer, and wait for every exchange."""
+        last = self.buckets[0]
         if acc_mode is not None:
-            T.grad_accumulate(self._accumulators()[0], self.small_bucket, acc_mode)
-        if exchange and self.world > 1 and not self.skip_allreduce:
+            T.grad_accumulate(self._accumulators()[0], last.grad, acc_mode)
+        if acc_mode in (None, 2) and self.world > 1 and not self.skip_allreduce:
+            if self.lora_rank is not None:
+                dist.all_reduce(last.grad)       # one small blocking exchange per optimizer step
+                return
             if not self.overlap_allreduce:
-                handles += [self._reduce(b) for b in reversed(self.layer_buckets)]
-            handles.append(self._reduce(self.small_bucket))
+                handles += [self._reduce(b.grad) for b in reversed(self.buckets[1:])]
+            handles.append(self._reduce(last.grad))
             for hd_ in handles:
                 if hd_ is not None:
                     hd_.wait()
-        if update:
-            self._finish_micro_step(acc_mode)
-        return loss
 
     def _finish_micro_step(self, acc_mode):
         """End of a step(update=True): the optimizer steps unless this was a micro-step before the last of its cycle."""
@@ -937,72 +998,6 @@ class Stage1Trainer:
             self.optimizer_step(micro_batches=self.accum_steps)
         else:
             self._micro += 1
-
-    def _lora_backward(self, f):
-        """Backward with the base frozen: the dX chain of the full backward without a single dW GEMM, and per adapted
-        projection dB = s dy^T u, du = s dy B, dA = du^T x, dx += du A.  Nothing that only feeds frozen parameters is
-        computed: no head / adaLN / embedder / embedding gradients, no dx below layer 0's qkv_proj.  `f`: step()'s locals."""
-        m, cfg, prep = self.model, self.cfg, f["prep"]
-        B, L, M, H, I = f["B"], f["L"], f["M"], f["H"], f["I"]
-        nq, nk, hd, nl, ntok, nf = f["nq"], f["nk"], f["hd"], f["nl"], f["ntok"], f["nf"]
-        hbuf, n1, qkv, ctx, h2, n2, gu, act, lse = (f[k] for k in ("hbuf", "n1", "qkv", "ctx", "h2", "n2", "gu", "act", "lse"))
-        u_q, u_o, sv, ck, rp, ls = f["u_q"], f["u_o"], f["sv"], f["ck"], self.lora_rp, self.lora_scale
-        lq, lo = f["lq"], f["lo"]
-        det = self.deterministic     # the discarded dgain / dmod sums too: one rule for every path
-        dy16 = T.unpatchify_bwd(f["dpred"])                                  # (Tn, 16)
-        dv = T.matmul(dy16, f["fl"].weight)                                  # (Tn, H)
-        dnrm = self._buf("dnrm", (M, H)); dnrm.zero_()
-        dmod = self._buf("dmod_scratch", (nf, 2 * H), F32); dmod.zero_()     # feeds adaLN only: discarded
-        T.ln_mod_bwd(dv, f["xhat"], f["rstd"], f["mod"], prep["x_rows"], dnrm, dmod, ntok, deterministic=det)
-        if f["head"] is not None:
-            dyin = T.unpatchify_bwd(f["dpred_in"])
-            dnrm.index_copy_(0, prep["c_idx"], T.matmul(dyin, f["head"].weight))
-        dgain = self._buf("dgain_scratch", (H,), F32); dgain.zero_()         # gain gradients of the frozen norms: discarded
-        dh = self._buf("dh", (M, H)); dh_b = self._buf("dh_b", (M, H))
-        T.rmsnorm_bwd(hbuf[nl], m.llm.norm.weight, dnrm, dh, dgain, m.llm.norm.variance_epsilon, deterministic=det)
-        dact = self._buf("dact", (M, I)); dgu = self._buf("dgu", (M, 2 * I)); dn = self._buf("dn", (M, H))
-        dctx = self._buf("dctx", (M, nq * hd)); dqkv = self._buf("dqkv", (M, (nq + 2 * nk) * hd))
-        delta = self._buf("delta", (B, nq, L), F32)
-        du = self._buf("du", (M, rp))
-        nsin = self._neg_sin(prep)
-        self.lora_bucket.zero_()     # a target module left out keeps zero gradients; every built one is overwritten
-        for li in range(nl - 1, -1, -1):
-            layer = m.llm.layers[li]
-            at, mlp = layer.self_attn, layer.mlp
-            if ck:
-                f["layer_forward"](li, with_output=False)
-            k = sv(li)
-            T.linear_dx(dh, mlp.down_proj.weight, None, out=dact)
-            T.silu_mul_bwd(gu[k], dact, dgu, mlp.act)
-            T.linear_dx(dgu, mlp.gate_up_proj.weight, None, out=dn)
-            T.rmsnorm_bwd(h2[k], layer.post_attention_layernorm.weight, dn, dh_b, dgain,
-                          layer.post_attention_layernorm.variance_epsilon, dres=dh, deterministic=det)   # dh2
-            T.linear_dx(dh_b, at.o_proj.weight, None, out=dctx)
-            if lo:
-                w, gr = self._lora_w[(li, "o_proj")], self._lora_g[(li, "o_proj")]
-                LO.lora_grad(dh_b, u_o[k], gr["B"], alpha=ls)                            # dB = s dy^T u
-                LO.lora_down(dh_b, w["B"], rp, s_is_k_by_rp=True, alpha=ls, out=du)      # du = s dy B
-                LO.lora_grad(ctx[k], du, gr["A"], transposed=True)                       # dA = du^T x
-                LO.lora_up_add(dctx, du, w["A"], s_is_rp_by_n=True)                      # dx += du A
-            T.attention_qkv_bwd(qkv[k].view(B, L, -1), ctx[k].view(B, L, -1), dctx.view(B, L, -1), lse[k], delta,
-                                dqkv.view(B, L, -1), prep["pm"], nq, nk, hd)
-            ops.rope_qk_inplace(dqkv, prep["rope"][0], nsin, nq, nk, hd)                 # inverse rotation
-            if lq:
-                w, gr = self._lora_w[(li, "qkv_proj")], self._lora_g[(li, "qkv_proj")]
-                LO.lora_grad(dqkv, u_q[k], gr["B"], alpha=ls)
-                LO.lora_down(dqkv, w["B"], rp, s_is_k_by_rp=True, alpha=ls, out=du)
-                LO.lora_grad(n1[k], du, gr["A"], transposed=True)
-            if li == 0:
-                break                # everything below layer 0's qkv_proj is frozen
-            T.linear_dx(dqkv, at.qkv_proj.weight, None, out=dn)
-            if lq:
-                LO.lora_up_add(dn, du, w["A"], s_is_rp_by_n=True)
-            T.rmsnorm_bwd(hbuf[li], layer.input_layernorm.weight, dn, dh, dgain, layer.input_layernorm.variance_epsilon,
-                          dres=dh_b, deterministic=det)                                  # dh (layer input)
-        if f["acc_mode"] is not None:
-            T.grad_accumulate(self._accumulators()[0], self.lora_bucket, f["acc_mode"])
-        if f["exchange"] and self.world > 1 and not self.skip_allreduce:
-            dist.all_reduce(self.lora_bucket)        # one small exchange per optimizer step
 
     def _neg_sin(self, prep):
         key = ("nsin", prep["rope"][1].data_ptr())
@@ -1042,13 +1037,9 @@ class Stage1Trainer:
         lr = self.current_lr()
         self.last_lr = lr
         self.step_count += 1
-        if self.lora_rank is not None:
-            self._lora_optimizer_step(lr, *self.betas, micro_batches=micro_batches)
-            return
         self.sumsq.zero_()
-        for b in self.layer_buckets:
-            T.sumsq(self._shard(b), self.sumsq)
-        T.sumsq(self._shard(self.small_bucket), self.sumsq)
+        for b in self.buckets[1:] + self.buckets[:1]:      # layers, then the small bucket: the order of the fp32 sum
+            T.sumsq(self._shard(b.grad), self.sumsq)
         partials = self.sumsq
         if self._sharded and not self.skip_allreduce:
             # every rank's sum over its reduced shards, in rank order, added on the device in a fixed order by clip_coef:
@@ -1059,66 +1050,35 @@ class Stage1Trainer:
         # buckets hold the sum over A micro-batches)
         T.clip_coef(partials, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w)
         b1, b2 = self.betas
-        if self._sharded:
-            self._sharded_update(lr, b1, b2)
-            return
-        ema_l = self.ema_layers if self.use_ema else [None] * len(self.layer_buckets)
-        ema_s = self.ema_small if self.use_ema else None
-        if not self.overlap_optimizer:
-            for i in range(len(self.layer_buckets)):
-                self._adamw(self.master_layers[i], self.param_layers[i], self.layer_buckets[i], self.m_layers[i],
-                            self.v_layers[i], ema_l[i], lr, b1, b2)
-            self._adamw(self.master_small, self.param_small, self.small_bucket, self.m_small, self.v_small, ema_s,
-                        lr, b1, b2)
-            return
-        # The update is a pure HBM stream (28 bytes per parameter) and the next step's forward is matrix work: they run side by
-        # side.  Everything below goes to the optimizer's stream behind the clip coefficient; the small bucket (embeddings,
-        # heads: read first) and then the layers in forward order, each followed by an event the next forward waits for right
-        # where it first reads that layer.  Readers outside step() call finish_optimizer() first.
-        main = torch.cuda.current_stream()
-        ready = torch.cuda.Event()
-        ready.record(main)
-        self._opt_stream.wait_event(ready)
-        with torch.cuda.stream(self._opt_stream):
-            self._adamw(self.master_small, self.param_small, self.small_bucket, self.m_small, self.v_small, ema_s,
-                        lr, b1, b2)
-            ev_small = torch.cuda.Event()
-            ev_small.record(self._opt_stream)
-            evs = []
-            for i in range(len(self.layer_buckets)):
-                self._adamw(self.master_layers[i], self.param_layers[i], self.layer_buckets[i], self.m_layers[i],
-                            self.v_layers[i], ema_l[i], lr, b1, b2)
-                e = torch.cuda.Event()
-                e.record(self._opt_stream)
-                evs.append(e)
-        self._opt_events = (ev_small, evs)
-
-    def _sharded_update(self, lr, b1, b2):
-        """AdamW on this rank's shard of every bucket, each bucket's bf16 parameters all-gathered in place right behind its
-        update: the small bucket first (embeddings and heads are read first), then the layers in forward order.  With
-        overlap_optimizer on the optimizer's stream behind the clip coefficient with an event per bucket, as in the
-        replicated update; the next forward waits for bucket i's event and gather where it first reads those parameters."""
-        ov = self.overlap_optimizer
+        # AdamW on this rank's shard of every bucket (the whole bucket when not sharded), sharded: the bucket's bf16 parameters
+        # all-gathered in place right behind its update.  The small bucket goes first (embeddings, heads: read first), then
+        # the layers in forward order.  overlap_optimizer: the update is a pure HBM stream (28 bytes per parameter) and the
+        # next step's forward is matrix work, so they run side by side: everything below goes to the optimizer's stream
+        # behind the clip coefficient, each bucket followed by an event the next forward waits for right where it first
+        # reads those parameters (_await_params).  Readers outside step() call finish_optimizer() first.
+        ov, order = self.overlap_optimizer, self.buckets
         if ov:
             ready = torch.cuda.Event()
             ready.record(torch.cuda.current_stream())
             self._opt_stream.wait_event(ready)
-        ema_l = self.ema_layers if self.use_ema else [None] * len(self.layer_buckets)
-        ema_s = self.ema_small if self.use_ema else None
-        buckets = [(self.master_small, self.param_small, self.small_bucket, self.m_small, self.v_small, ema_s)]
-        buckets += list(zip(self.master_layers, self.param_layers, self.layer_buckets, self.m_layers, self.v_layers, ema_l))
+        elif not self._sharded:
+            order = self.buckets[1:] + self.buckets[:1]      # nobody waits per bucket: the launch order this path always had
         evs, works = [], []
         with torch.cuda.stream(self._opt_stream if ov else torch.cuda.current_stream()):
-            for master, param, grad, m_, v_, ema in buckets:
-                self._adamw(master, self._shard(param), self._shard(grad), m_, v_, ema, lr, b1, b2)
-                works.append(None if self.skip_allreduce else
-                             SPM.all_gather_flat(self._shard(param), self._group, out=param, async_op=True))
+            for b in order:
+                self._adamw(b.master, self._shard(b.param), self._shard(b.grad), b.m, b.v, b.ema if self.use_ema else None,
+                            lr, b1, b2)      # `use_ema` stays the live switch: scripts/accum_ema_step_time.py flips it
+                if self._sharded:
+                    works.append(None if self.skip_allreduce else
+                                 SPM.all_gather_flat(self._shard(b.param), self._group, out=b.param, async_op=True))
                 if ov:
                     e = torch.cuda.Event()
                     e.record(self._opt_stream)
                     evs.append(e)
-        self._opt_events = (evs[0], evs[1:]) if ov else None
-        self._gathers = (works[0], works[1:])
+        # (small, [layer 0 .. nl-1]); a LoRA trainer's layers all wait for the one adapter event
+        self._opt_events = (evs[0], evs[1:] or [evs[0]] * self.cfg.num_hidden_layers) if ov else None
+        if self._sharded:
+            self._gathers = (works[0], works[1:])
 
     def finish_optimizer(self):
         """Makes the current stream wait for the update in flight (overlap_optimizer) and for the parameter all-gathers
@@ -1133,7 +1093,6 @@ class Stage1Trainer:
                     w.wait()
             self._gathers = None
 
-
     # ---- checkpoints (LVM/train/train_x1_stage1_noiseinput.py:304-334,437-451: accelerate's checkpoint-{step}
     #      directories with auto-resume from the highest step).  Written with safetensors, nothing is unpickled on
     #      load: model.safetensors holds the bf16 state_dict under the reference's keys (loadable by
@@ -1141,24 +1100,25 @@ class Stage1Trainer:
     def _optimizer_tensors(self):
         """(tensor of this trainer, optimizer.safetensors key, unpadded bucket length) of every optimizer-state tensor; the
         tensor is this rank's shard when sharded, else the whole bucket."""
-        pairs = [(self.master_small, "master_small", self._small_numel), (self.m_small, "m_small", self._small_numel),
-                 (self.v_small, "v_small", self._small_numel)]
-        for i, n in enumerate(self._bucket_numel):
-            pairs += [(self.master_layers[i], f"master.{i}", n), (self.m_layers[i], f"m.{i}", n),
-                      (self.v_layers[i], f"v.{i}", n)]
-        return pairs
+        return [(getattr(b, kind), self._state_key(b, kind), b.numel) for b in self.buckets for kind in ("master", "m", "v")]
 
     def _ema_tensors(self):
         """_optimizer_tensors' triples of the EMA buffers (none without use_ema): ema_small / ema.{i} beside master.*."""
-        if not self.use_ema:
-            return []
-        return [(self.ema_small, "ema_small", self._small_numel)] + \
-               [(self.ema_layers[i], f"ema.{i}", n) for i, n in enumerate(self._bucket_numel)]
+        return [(b.ema, self._state_key(b, "ema"), b.numel) for b in self.buckets if b.ema is not None]
 
-    def _schedule_record(self):
-        return {"lr_scheduler": self.lr_scheduler, "lr_warmup_steps": self.lr_warmup_steps,
-                "lr_num_training_steps": self.lr_num_training_steps, "lr_num_cycles": self.lr_num_cycles,
-                "lr_power": self.lr_power, "gradient_accumulation_steps": self.accum_steps}
+    @staticmethod
+    def _state_key(b: _Bucket, kind: str) -> str:
+        """optimizer.safetensors key of bucket b's `kind` tensor: master_small, m.{i}, ema.{i}, lora_master, ..."""
+        return f"{kind}_small" if b.key == "small" else f"lora_{kind}" if b.key == "lora" else f"{kind}.{b.key}"
+
+    def _write_trainer_state(self, path: str, step: int, **mode):
+        """trainer_state.json of a checkpoint directory; `mode`: the fields only a full / only a LoRA trainer records."""
+        with open(os.path.join(path, "trainer_state.json"), "w") as f:
+            json.dump({"step_count": self.step_count, "global_step": step, "lr": self.lr, "weight_decay": self.wd,
+                       "betas": list(self.betas), "eps": self.eps, "lr_scheduler": self.lr_scheduler,
+                       "lr_warmup_steps": self.lr_warmup_steps, "lr_num_training_steps": self.lr_num_training_steps,
+                       "lr_num_cycles": self.lr_num_cycles, "lr_power": self.lr_power,
+                       "gradient_accumulation_steps": self.accum_steps, **mode}, f)
 
     # ---- EMA weights -------------------------------------------------------------------------------------------------
     def _ema_flat(self, t):
@@ -1170,8 +1130,7 @@ class Stage1Trainer:
         """(EMA tensor, flat bf16 parameter buffer, parameter names in buffer order) per bucket, the small one first."""
         if not self.use_ema:
             raise VgptError("this trainer keeps no EMA (use_ema=False)")
-        return [(self.ema_small, self.param_small, self.small_names)] + \
-               list(zip(self.ema_layers, self.param_layers, self.layer_names))
+        return [(b.ema, b.param, b.names) for b in self.buckets]
 
     def ema_state_dict(self) -> Dict[str, torch.Tensor]:
         """The EMA weights as a bf16 state dict under the reference's parameter keys (what train...py:440-447 saves from
@@ -1236,8 +1195,6 @@ class Stage1Trainer:
             raise VgptError(f"save_checkpoint in the middle of an accumulation cycle (micro-step {self._micro} of "
                             f"{self.accum_steps}): checkpoints are written on optimizer-step boundaries")
         self.finish_optimizer()
-        import json
-        import os
         from safetensors.torch import save_file
         step = self.step_count if global_step is None else int(global_step)
         path = os.path.join(results_dir, f"checkpoint-{step}")
@@ -1266,10 +1223,7 @@ class Stage1Trainer:
             save_file(opt, os.path.join(path, "optimizer.safetensors"))
             if ema_sd is not None:
                 save_file({k: v.detach().cpu().contiguous() for k, v in ema_sd.items()}, os.path.join(path, "ema.safetensors"))
-            with open(os.path.join(path, "trainer_state.json"), "w") as f:
-                json.dump({"step_count": self.step_count, "global_step": step, "lr": self.lr, "weight_decay": self.wd,
-                           "betas": list(self.betas), "eps": self.eps, **self._schedule_record(),
-                           "use_ema": self.use_ema, "ema_decay": self.ema_decay, "small_names": self.small_names}, f)
+            self._write_trainer_state(path, step, use_ema=self.use_ema, ema_decay=self.ema_decay, small_names=self.small_names)
         if distributed:
             dist.barrier()
         return path
@@ -1285,8 +1239,6 @@ class Stage1Trainer:
         without EMA ignores them.  The checkpoint's gradient_accumulation_steps is a record only: resuming with another
         value is allowed, the optimizer state does not depend on it.  An accumulation cycle under way is dropped."""
         self.finish_optimizer()
-        import json
-        import os
         from safetensors.torch import load_file
         with open(os.path.join(path, "trainer_state.json")) as f:
             st = json.load(f)
@@ -1327,8 +1279,8 @@ class Stage1Trainer:
         self.last_load = {"ema": "none" if not ema_pairs else "restored" if ema_in_file else "initialised from master"}
         if ema_pairs and not ema_in_file:
             import logging
-            for ema, master in zip([self.ema_small] + self.ema_layers, [self.master_small] + self.master_layers):
-                ema.copy_(master)
+            for b in self.buckets:
+                b.ema.copy_(b.master)
             logging.getLogger(__name__).warning("%s holds no EMA tensors: the EMA starts as a copy of the loaded master weights",
                                                 path)
         with torch.no_grad():     # parameters are views of the flat bf16 buffers: copy in place, keep the views
@@ -1353,24 +1305,17 @@ class Stage1Trainer:
     # LoRA mode: peft's adapter directory (adapter_model.safetensors + adapter_config.json; layout written from knowledge of
     # peft's format, parity unpinned: DESIGN.md §6a) next to this trainer's own optimizer.safetensors / trainer_state.json
     def _save_lora(self, path: str, step: int):
-        import json
-        import os
         from safetensors.torch import save_file
         from .lora import adapter_config
         os.makedirs(path, exist_ok=True)
         save_file({k: v.detach().cpu().contiguous() for k, v in self.lora.items()}, os.path.join(path, "adapter_model.safetensors"))
         with open(os.path.join(path, "adapter_config.json"), "w") as f:
             json.dump(adapter_config(self.lora_rank, self.lora_alpha, self.lora_targets), f, indent=2)
-        save_file({"lora_master": self.lora_master.cpu(), "lora_m": self.lora_m.cpu(), "lora_v": self.lora_v.cpu()},
-                  os.path.join(path, "optimizer.safetensors"))
-        with open(os.path.join(path, "trainer_state.json"), "w") as f:
-            json.dump({"step_count": self.step_count, "global_step": step, "lr": self.lr, "weight_decay": self.wd,
-                       "betas": list(self.betas), "eps": self.eps, **self._schedule_record(),
-                       "lora": {"r": self.lora_rank, "rp": self.lora_rp, "lora_alpha": self.lora_alpha,
-                                "target_modules": list(self.lora_targets), "numel": self._lora_numel}}, f)
+        save_file({key: t.cpu() for t, key, _ in self._optimizer_tensors()}, os.path.join(path, "optimizer.safetensors"))
+        self._write_trainer_state(path, step, lora={"r": self.lora_rank, "rp": self.lora_rp, "lora_alpha": self.lora_alpha,
+                                                    "target_modules": list(self.lora_targets), "numel": self._lora_numel})
 
     def _load_lora(self, path: str, st):
-        import os
         from safetensors.torch import load_file
         from .lora import load_adapter
         rec = st["lora"]
@@ -1397,7 +1342,6 @@ class Stage1Trainer:
     def auto_resume(self, results_dir: str) -> Optional[int]:
         """Load the checkpoint-{N} with the largest N under results_dir, if any (train...stage1.py:304-315)."""
         import glob
-        import os
         found = [d for d in glob.glob(os.path.join(results_dir, "checkpoint-*")) if d.rsplit("-", 1)[-1].isdigit()]
         if not found:
             return None
