@@ -6,7 +6,7 @@ v_cvt_pk_bf16_f32, ~30 one-cycle-class integer / move instructions).  The matrix
 many cycles each ingredient costs alone, what the sum costs in program order with the real register dependencies
 (MFMA -> softmax -> MFMA), what a perfect interleave inside one wave costs, and what a SECOND wave on the SIMD recovers.
 
-  python scripts/attn_issue_probe.py --build     (here: writes csrc/experiments/issue_probe_gen.hip, compiles libvgpt_x_issue.so)
+  python scripts/attn_issue_probe.py --build     (here: writes csrc/build/issue_probe_gen.hip, compiles libvgpt_x_issue.so)
   python scripts/attn_issue_probe.py             (GPU box: runs every variant at 1 and 2 waves per SIMD, JSON lines)
 """
 import ctypes, json, os, subprocess, sys
@@ -230,7 +230,8 @@ def build():
     for name, (b0, b1) in S2.items():
         src += KERNEL2 % {"name": name, "body0": fmt(b0), "body1": fmt(b1)}
     src += HOST % {"ptrs": ", ".join("probe_" + n for n in list(V) + list(S2)), "nsingle": len(V)}
-    path = os.path.join(CSRC, "experiments", "issue_probe_gen.hip")
+    os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
+    path = os.path.join(CSRC, "build", "issue_probe_gen.hip")
     open(path, "w").write(src)
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, path], check=True)
     print("built", SO, "variants:", ", ".join(V))

@@ -60,11 +60,6 @@ __device__ __forceinline__ void tile_sync() {
     asm volatile("" ::: "memory");
 }
 constexpr int LIST_MAX = 1023;  // active tiles per list chunk (4 KiB of LDS)
-// VGPT_BWD_EXPERIMENT (diagnostic builds of the dK/dV kernels, results are WRONG): 1 = no element-wise math,
-// 2 = transposed fragments read once, 3 = no statistics / mask DMA, 4 = no Q/dO DMA after the first tile
-#ifndef VGPT_BWD_EXPERIMENT
-#define VGPT_BWD_EXPERIMENT 0
-#endif
 
 // row read of a swizzled [row][192 B] image: lane (r = row, h) gets elements [16s + 8h, +8)
 __device__ __forceinline__ bf16x8 row_frag(const char* img, int row, int s, int h) {
@@ -300,10 +295,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(BwdArgs a) {
 // ------------------------------------------------------------------------------------------------------
 // dK, dV: block = 4 waves = 128 keys of one (batch, kv head); Q/dO tiles of 64 query rows in LDS
 // ------------------------------------------------------------------------------------------------------
-// WANT_DK / WANT_DV: both gradients in one launch need ~380 VGPRs (one wave per SIMD); each alone fits the 256-register
-// budget of two waves per SIMD at the price of recomputing S = Q K^T.  Both forms are built (see the launch below).
-template <bool WANT_DK, bool WANT_DV>
-__global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dkv_kernel(BwdArgs a) {
+// Both gradients in one launch need ~380 VGPRs (one wave per SIMD); one launch per gradient at two waves per SIMD, each
+// recomputing S = Q K^T, measured slower (stage-1 attention backward).
+__global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(BwdArgs a) {
     // stage: Q image | dO image | lse[64] | delta[64] | mask words [64][4]
     constexpr int STAT_OFF = 2 * TILE_BYTES, MASK_OFF = STAT_OFF + 512, STAGE = MASK_OFF + 1024;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -326,7 +320,7 @@ __global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dk
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         Kf[s] = *reinterpret_cast<const bf16x8*>(kp + 16 * s + 8 * h);
-        if constexpr (WANT_DK) Vf[s] = *reinterpret_cast<const bf16x8*>(vp + 16 * s + 8 * h);
+        Vf[s] = *reinterpret_cast<const bf16x8*>(vp + 16 * s + 8 * h);
     }
     f32x16 dK[DT], dV[DT];
 #pragma unroll
@@ -349,7 +343,7 @@ __global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dk
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         asm volatile("" : "+v"(Kf[s]));
-        if constexpr (WANT_DK) asm volatile("" : "+v"(Vf[s]));
+        asm volatile("" : "+v"(Vf[s]));
     }
 
     for (int gh = 0; gh < a.kv_group; ++gh) {
@@ -374,7 +368,6 @@ __global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dk
                 dma16(dobase + (int64_t)row * a.do_ss + g_chunk[j] * 8, sq + TILE_BYTES + off);
             }
             // row statistics and mask words also arrive by LDS-DMA (4-byte form)
-            if (VGPT_BWD_EXPERIMENT == 3) return;
             if (wave == 0) {
                 const int row = min(qt * 64 + lane, a.L - 1);
                 dma4(lse_b + row, sq + STAT_OFF);
@@ -413,7 +406,7 @@ __global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dk
         for (int it = 0; it < n_act; ++it) {
             tile_sync();
             const uint32_t e_n2 = it + 2 < n_act ? alist[3 + it] : 0u;
-            if (it + 1 < n_act && VGPT_BWD_EXPERIMENT != 4) stage(buf ^ 1, (int)(e_nxt >> 8));
+            if (it + 1 < n_act) stage(buf ^ 1, (int)(e_nxt >> 8));
             const int qt = (int)(e_cur >> 8);
             const int codes = (e_cur >> (4 * (wave >> 1))) & 15;
             const char* sq = smem + buf * STAGE;
@@ -434,7 +427,7 @@ __global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dk
 #pragma unroll
                     for (int s = 0; s < KS; ++s) S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Qr[s], Kf[s], S, 0, 0, 0);
                 }
-                if constexpr (WANT_DK) {
+                {   // dP = dO V^T (the scope ends dOr's live range)
                     bf16x8 dOr[KS];
 #pragma unroll
                     for (int s = 0; s < KS; ++s) dOr[s] = row_frag(sdo, qh * 32 + r, s, h);
@@ -443,14 +436,10 @@ __global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dk
                 }
                 // transposed operand for dV^T += dO^T P (k index = query row); requested before the element-wise math
                 bf16x8 dOt[DT][2];
-                if constexpr (WANT_DV) {
-                    if (VGPT_BWD_EXPERIMENT != 2 || it == 0) {
 #pragma unroll
-                        for (int dt = 0; dt < DT; ++dt)
+                for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
-                            for (int t = 0; t < 2; ++t) dOt[dt][t] = tr_frag(sdo, qh * 32 + t * 16, dt, lane);
-                    }
-                }
+                    for (int t = 0; t < 2; ++t) dOt[dt][t] = tr_frag(sdo, qh * 32 + t * 16, dt, lane);
                 __builtin_amdgcn_sched_barrier(0);
                 // accumulator register i holds query row qh*32 + 8 (i>>2) + 4h + (i&3): the row statistics of four
                 // consecutive registers are one 16-byte LDS read
@@ -458,12 +447,11 @@ __global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dk
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     lse4[g4] = *reinterpret_cast<const f32x4*>(st + qh * 32 + 8 * g4 + 4 * h);
-                    if constexpr (WANT_DK) dlt4[g4] = *reinterpret_cast<const f32x4*>(st + 64 + qh * 32 + 8 * g4 + 4 * h);
+                    dlt4[g4] = *reinterpret_cast<const f32x4*>(st + 64 + qh * 32 + 8 * g4 + 4 * h);
                 }
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    if (VGPT_BWD_EXPERIMENT == 1) continue;
-                    dP[i] = WANT_DK ? dP[i] - dlt4[i >> 2][i & 3] : 0.f;                                      // dP - delta
+                    dP[i] = dP[i] - dlt4[i >> 2][i & 3];                                                      // dP - delta
                     S[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(S[i], a.scale_log2e, -lse4[i >> 2][i & 3]));  // P
                 }
                 if (code == 2) {  // mixed tile: bit r of the word of (query row, this wave's 32 keys)
@@ -490,15 +478,13 @@ __global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dk
                     }
                 }
                 // S now holds P; dP holds dP - delta.  dS / scale = P (dP - delta) goes to dP, P stays in S.
-                if constexpr (WANT_DK) {
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) dP[i] = S[i] * dP[i];   // the softmax scale multiplies dK once, in the epilogue
-                }
+                for (int i = 0; i < 16; ++i) dP[i] = S[i] * dP[i];   // the softmax scale multiplies dK once, in the epilogue
                 // no MFMA of the products below starts while the packed fp32 instructions above are in flight
                 // (scripts/attn_issue_probe.py: a v_pk_* beside an MFMA costs 53 cycles a group instead of 32; hipcc interleaved
                 // them): whole backward 866 / 875 against 880 / 881 us at the cfg-3 mask, scripts/attn_bwd_probe.py
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (WANT_DV) {
+                {   // dV^T += dO^T P
                     bf16x8 Pf[2];
 #pragma unroll
                     for (int t = 0; t < 2; ++t) Pf[t] = pack8(S, t);
@@ -508,7 +494,7 @@ __global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dk
                         for (int t = 0; t < 2; ++t)
                             dV[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dOt[dt][t], Pf[t], dV[dt], 0, 0, 0);
                 }
-                if constexpr (WANT_DK) {  // dK^T += Q^T dS
+                {   // dK^T += Q^T dS
                     bf16x8 dSf[2];
 #pragma unroll
                     for (int t = 0; t < 2; ++t) dSf[t] = pack8(dP, t);
@@ -542,8 +528,8 @@ __global__ __launch_bounds__(256, (WANT_DK && WANT_DV) ? 1 : 2) void attn_bwd_dk
                     ok[t] = f2bf(dK[dt][4 * g4 + t] * a.scale);
                     ov[t] = f2bf(dV[dt][4 * g4 + t]);
                 }
-                if constexpr (WANT_DK) *reinterpret_cast<bf16x4*>(kp_o + dt * 32 + 8 * g4 + 4 * h) = ok;
-                if constexpr (WANT_DV) *reinterpret_cast<bf16x4*>(vp_o + dt * 32 + 8 * g4 + 4 * h) = ov;
+                *reinterpret_cast<bf16x4*>(kp_o + dt * 32 + 8 * g4 + 4 * h) = ok;
+                *reinterpret_cast<bf16x4*>(vp_o + dt * 32 + 8 * g4 + 4 * h) = ov;
             }
     }
 }
@@ -580,13 +566,8 @@ VGPT_EXPORT int vgpt_attn_blockmask_bwd(const void* q, const void* k, const void
     constexpr int lds_dq = 2 * 2 * TILE_BYTES + 4096 + 2048, lds_dkv = 2 * (2 * TILE_BYTES + 512 + 1024) + 4096;
     if (!attr_set) {
         hipError_t e1 = hipFuncSetAttribute((const void*)attn_bwd_dq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dq);
-        hipError_t e2 = hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<true, false>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_dkv);
-        hipError_t e3 = hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<false, true>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_dkv);
-        hipError_t e4 = hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<true, true>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_dkv);
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
+        hipError_t e2 = hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dkv);
+        if (e1 != hipSuccess || e2 != hipSuccess) {
             vgpt_set_error("vgpt_attn_blockmask_bwd: hipFuncSetAttribute failed");
             return VGPT_ERR_HIP;
         }
@@ -597,16 +578,7 @@ VGPT_EXPORT int vgpt_attn_blockmask_bwd(const void* q, const void* k, const void
                        a.L, n_heads, a.o_sb, a.o_sh, a.o_ss, a.do_sb, a.do_sh, a.do_ss);
     hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(a.nqb * n_heads * a.B), dim3(256), lds_dq, st, a);
     const dim3 grid_kv((unsigned)(cdiv(L, 128) * n_kv_heads * B));
-    // dK and dV in one launch (one wave per SIMD, ~380 VGPRs) measured 5 % faster than two launches at two waves per
-    // SIMD that each recompute S (927 vs 971 us on the cfg-3 mask); VGPT_ATTN_BWD_SPLIT=1 selects the latter for A/B runs
-    static int split = -1;
-    if (split < 0) { const char* e = getenv("VGPT_ATTN_BWD_SPLIT"); split = e ? atoi(e) : 0; }
-    if (!split) {
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, true>), grid_kv, dim3(256), lds_dkv, st, a);
-    } else {
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, true>), grid_kv, dim3(256), lds_dkv, st, a);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, false>), grid_kv, dim3(256), lds_dkv, st, a);
-    }
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid_kv, dim3(256), lds_dkv, st, a);
     VGPT_CHECK_LAUNCH("vgpt_attn_blockmask_bwd");
     return VGPT_OK;
 }

@@ -24,25 +24,8 @@
 
 #include "common.h"
 
-// Softmax arithmetic of the tile loop.  0 (product): the plain online softmax.  1: three arithmetic reductions, built to
-// parity and measured on the same box (`make attn-variant-VGPT_ATTN_LAZY`, round 3) -- an EXPERIMENT, not in the product:
-//   (a) scale * log2(e) folded into Q once per work item (Q' = bf16(Q * c)), so a score needs no multiply;
-//   (b) the running reference m_ref of a query row is LAZY: the score accumulators start at -m_ref (the C operand of the
-//       first QK^T MFMA is a register block holding -m_ref) so that P = exp2(S) directly -- no subtract, no per-tile
-//       alpha -- and the reference moves (and O, l are rescaled) only when a tile's largest score exceeds it by more than
-//       LAZY_THRESH (2^8: P <= 256, far inside fp32 / bf16 range) or when the row sees its first key;
-//   (c) the row sums l come from the matrix pipe: one more 32-row output tile of P V with an all-ones V block.
-// Per tile and wave it issues 16 v_max3 + 32 v_exp + 16 v_cvt_pk and 28 MFMAs where the plain form issues 16 v_max3 +
-// 16 v_pk_fma + 32 v_exp + 16 v_pk_add + 16 v_cvt_pk + the alpha bookkeeping and 24 MFMAs: a third fewer vector issue
-// cycles.  Measured (cfg-2 live rows, in the step's own launch order, same box): 148.7 / 151.3 us against 155.9 us -- 3-5 %,
-// 0.15 ms of a 31 ms step: the loop is not bound by what it issues.  And (a) costs accuracy exactly where logits are large:
-// Q' is a second rounding of Q, an error proportional to the score; tests/test_ops_gpu.py::test_attention_late_spike
-// (keys 30x the usual norm, scores ~ 400 in log2 units) keeps rel-L2 < 1e-2 but its max-abs bound reads 0.135 against
-// 0.06.  Without (a) the multiply stays and nothing is saved.  Not worth the accuracy: the product keeps the plain form.
-#ifndef VGPT_ATTN_LAZY
-#define VGPT_ATTN_LAZY 0
-#endif
-#define LAZY_THRESH 8.0f
+// The tile loop is the plain online softmax.  The lazy-reference softmax and the compiler-pipelined loop that round 3 built
+// and measured against it (neither adopted) are described, with their figures, in DESIGN.md section 4b.
 // Diagnostics build (make attn-variant-VGPT_ATTN_STAMPS, scripts/attn_stamps.py; results unchanged, timing perturbed by
 // ~4 x 50 cycles per tile): wave 0 of every workgroup sums, over its tiles, the shader cycles (s_memtime) of four stretches
 // of the loop -- top of the iteration -> behind the barrier | -> QK^T MFMAs issued | -> softmax done | -> P V issued -- into
@@ -50,12 +33,6 @@
 #ifndef VGPT_ATTN_STAMPS
 #define VGPT_ATTN_STAMPS 0
 #endif
-// Round 3 also built a software-pipelined form of the tile loop (the QK^T MFMAs of tile t+1 issued inside the softmax of
-// tile t through sched_group_barrier, K one tile ahead of V in the same two staging buffers; 252 registers, parity-green on
-// the whole suite) and measured it SLOWER on the same box: 162.8 / 163.5 us against 151.3 us per layer at the cfg-2 live
-// rows (31.75 vs 31.51 ms per step).  Overlapping a wave's own matrix and vector work does not help a loop whose two
-// waves per SIMD already fill the issue port between them (active_inst_any 0.39 per wave, profiles/r02_pmc_mfma.json);
-// kept out of the product as csrc/experiments/attn_fwd_pipelined_loop.inc.
 
 #include "attn_p2_loop.inc"
 #define VGPT_P2_DRAIN_0_M VGPT_P2_DRAIN_0
@@ -231,30 +208,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (D <= 96 ? 2 : 1))) void at
     bf16x8 Qf[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) Qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s + 8 * h);
-#if VGPT_ATTN_LAZY
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) Qf[s][j] = f2bf(bf2f(Qf[s][j]) * a.scale_log2e);
-#endif
 
     f32x16 O[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) O[dt][i] = 0.f;
-#if VGPT_ATTN_LAZY
-    f32x16 Ol, Cm;      // row sums (every register of a lane: l of its query row); -m_ref, the C operand of S^T's first MFMA
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { Ol[i] = 0.f; Cm[i] = 0.f; }
-    float m_ref = 0.f;
-    bool need_ref = true;   // this row has not seen a key yet: the first finite tile maximum becomes its reference
-    bf16x8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ones[j] = f2bf(1.0f);
-#else
     float m_i = -INFINITY, l_i = 0.f;
-#endif
 
     // ---- staging helpers ----
     constexpr bool GLDS = TR && C::GLDS;
@@ -349,10 +309,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (D <= 96 ? 2 : 1))) void at
     // inside the tile loop and the vmcnt(0) emitted for it would also drain the (asm-issued) LDS-DMA in flight.
 #pragma unroll
     for (int s = 0; s < KS; ++s) asm volatile("" : "+v"(Qf[s]));
-#ifdef VGPT_ATTN_PRIO
-    // experiment (make attn-variant-VGPT_ATTN_PRIO VAL=n): a static s_setprio 1 for one of the two workgroups of a CU
-    if constexpr (P2) { if ((blockIdx.x >> VGPT_ATTN_PRIO) & 1) __builtin_amdgcn_s_setprio(1); }
-#endif
     if constexpr (P2) asm volatile(VGPT_P2_INIT ::: VGPT_P2_CLOBBERS);
     for (int chunk0 = 0; chunk0 < a.nkt; chunk0 += ACT_MAX) {
     __syncthreads();  // every wave is done with the previous list and the staging buffers
@@ -418,18 +374,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (D <= 96 ? 2 : 1))) void at
             f32x16 S[2];
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
-#if VGPT_ATTN_LAZY
-                S[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Kf[kb][0], Qf[0], Cm, 0, 0, 0);   // S starts at -m_ref
-#pragma unroll
-                for (int s = 1; s < KS; ++s)
-                    S[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Kf[kb][s], Qf[s], S[kb], 0, 0, 0);
-#else
 #pragma unroll
                 for (int i = 0; i < 16; ++i) S[kb][i] = 0.f;
 #pragma unroll
                 for (int s = 0; s < KS; ++s)
                     S[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Kf[kb][s], Qf[s], S[kb], 0, 0, 0);
-#endif
             }
             STAMP(sC);
             // ---- V^T fragments do not depend on the softmax: request them now so their LDS latency hides
@@ -484,35 +433,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (D <= 96 ? 2 : 1))) void at
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) mxp[kb] = fmaxf(mxp[kb], S[kb][i]);
-#if VGPT_ATTN_LAZY
-            // scores are in log2 units relative to the row's reference already: P = exp2(S) as it stands, unless a row
-            // outgrew its reference (or has none yet) -- then that row's reference moves to the tile maximum
-            const float mx = half_max(fmaxf(mxp[0], mxp[1]));
-            if (__any(need_ref || mx > LAZY_THRESH)) {
-                const bool fin = mx > -INFINITY;
-                const float delta = need_ref ? (fin ? mx : 0.f) : (mx > LAZY_THRESH ? mx : 0.f);
-                const float alpha = need_ref ? 1.f : __builtin_amdgcn_exp2f(-delta);   // a row without a key holds O = l = 0
-                need_ref = need_ref && !fin;
-                m_ref += delta;
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) S[kb][i] -= delta;
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) O[dt][i] *= alpha;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    Ol[i] *= alpha;
-                    Cm[i] = -m_ref;
-                }
-            }
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) S[kb][i] = __builtin_amdgcn_exp2f(S[kb][i]);
-#else
             const float mx = half_max(fmaxf(mxp[0], mxp[1])) * a.scale_log2e;  // scale > 0: max commutes with it
             const float m_new = fmaxf(m_i, mx);
             const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
@@ -544,7 +464,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (D <= 96 ? 2 : 1))) void at
                     for (int i = 0; i < 16; ++i) O[dt][i] *= alpha;
             }
             m_i = m_new;
-#endif
             STAMP(sD);
             // ---- P^T fragments: accumulator registers 8*half..8*half+7 of S[kb] ----
             bf16x8 Pf[4];
@@ -558,10 +477,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (D <= 96 ? 2 : 1))) void at
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
                     O[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Vf[dt][t], Pf[t], O[dt], 0, 0, 0);
-#if VGPT_ATTN_LAZY
-#pragma unroll
-            for (int t = 0; t < 4; ++t) Ol = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, Pf[t], Ol, 0, 0, 0);   // l += sum_k P
-#endif
 #if VGPT_ATTN_STAMPS
             {
                 STAMP(sE);
@@ -720,9 +635,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : (D <= 96 ? 2 : 1))) void at
 #endif
     }
     // ---- epilogue: lane holds O^T[d = 32dt + (i&3) + 8(i>>2) + 4h][q = r] ----
-#if VGPT_ATTN_LAZY
-    const float l_i = Ol[0], m_i = m_ref;   // every register of Ol holds the lane's row sum (all 64 keys of a tile: no half-sum)
-#endif
     int lane_e = threadIdx.x & 63;
     if constexpr (P2) asm volatile("" : "+v"(lane_e));   // the hand-scheduled kernel leaves hipcc 64 registers in the tile loop: the
     const int r_e = lane_e & 31, h_e = lane_e >> 5;      // epilogue's lane-derived values are formed here, not carried through it
@@ -804,73 +716,91 @@ struct ItemPlan {
     int item_rows;   // upper bound of the items' row counts: 128 (4-wave kernel) or 256 (8-wave kernel, head dim 96)
 };
 
-static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, float* lse, int64_t q_start,
-                         const uint32_t* bits, const uint8_t* summary, const int32_t* order, const ItemPlan* plan,
-                         int64_t B,
-                         int64_t L, int n_heads, int n_kv_heads, int head_dim,
-                         int64_t q_sb, int64_t q_sh, int64_t q_ss, int64_t k_sb,
-                         int64_t k_sh, int64_t k_ss, int64_t v_sb, int64_t v_sh,
-                         int64_t v_ss, int64_t o_sb, int64_t o_sh, int64_t o_ss,
-                         float scale, int variant, void* stream) {
-    VGPT_REQUIRE(q && k && v && o && bits && (summary || plan), VGPT_ERR_INVALID,
+// One forward call as the exported entry points describe it: first what every entry point takes, in the order of its
+// parameter list, then what only some of them take.
+struct AttnCall {
+    const void *q, *k, *v;
+    void* o;
+    const uint32_t* bits;
+    int64_t B, L;
+    int n_heads, n_kv_heads, head_dim;
+    int64_t q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss;
+    float scale;
+    void* stream;
+    const uint8_t* summary = nullptr;   // per (128-row q block, key tile); null with a plan
+    const int32_t* order = nullptr;
+    const ItemPlan* plan = nullptr;
+    float* lse = nullptr;
+    int64_t q_start = 0;
+    int variant = 0;
+};
+
+using AttnLaunch = int (*)(const AttnArgs&, hipStream_t);
+
+// The one launch decision.  item_rows: the plan's, 128 without a plan; hand_scheduled: attn_p2_enabled().
+static int attn_fwd_select(int head_dim, int variant, int item_rows, bool hand_scheduled, AttnLaunch* fn) {
+    if (item_rows == 256) {
+        VGPT_REQUIRE(head_dim == 96 && variant == 0, VGPT_ERR_UNSUPPORTED,
+                     "vgpt_attn_fwd_plan: 256-row items need head_dim 96 (got %d)", head_dim);
+        *fn = launch<96, true, 8>;
+        return VGPT_OK;
+    }
+    const bool tr = variant == 0;
+    switch (head_dim) {
+        case 64: *fn = tr ? launch<64, true> : launch<64, false>; return VGPT_OK;
+        case 96: *fn = !tr ? launch<96, false> : hand_scheduled ? launch<96, true, 4, true> : launch<96, true>; return VGPT_OK;
+        case 128: *fn = tr ? launch<128, true> : launch<128, false>; return VGPT_OK;
+    }
+    return VGPT_ERR_UNSUPPORTED;
+}
+
+static int attn_fwd_impl(const AttnCall& c) {
+    const ItemPlan* plan = c.plan;
+    VGPT_REQUIRE(c.q && c.k && c.v && c.o && c.bits && (c.summary || plan), VGPT_ERR_INVALID,
                  "vgpt_attn_blockmask_fwd: null pointer");
-    VGPT_REQUIRE(B >= 0 && L >= 0 && n_heads > 0 && n_kv_heads > 0, VGPT_ERR_INVALID,
+    VGPT_REQUIRE(c.B >= 0 && c.L >= 0 && c.n_heads > 0 && c.n_kv_heads > 0, VGPT_ERR_INVALID,
                  "vgpt_attn_blockmask_fwd: bad shape");
-    VGPT_REQUIRE(n_heads % n_kv_heads == 0, VGPT_ERR_INVALID,
+    VGPT_REQUIRE(c.n_heads % c.n_kv_heads == 0, VGPT_ERR_INVALID,
                  "vgpt_attn_blockmask_fwd: n_kv_heads must divide n_heads");
-    VGPT_REQUIRE(vgpt_attn_supported(head_dim), VGPT_ERR_UNSUPPORTED,
-                 "vgpt_attn_blockmask_fwd: head_dim=%d unsupported (64, 96, 128)", head_dim);
-    VGPT_REQUIRE(scale > 0.f, VGPT_ERR_INVALID, "vgpt_attn_blockmask_fwd: scale must be positive");
-    VGPT_REQUIRE(variant == 0 || variant == 1, VGPT_ERR_INVALID,
-                 "vgpt_attn_blockmask_fwd: unknown variant %d", variant);
-    const int64_t strides[] = {q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss};
+    VGPT_REQUIRE(vgpt_attn_supported(c.head_dim), VGPT_ERR_UNSUPPORTED,
+                 "vgpt_attn_blockmask_fwd: head_dim=%d unsupported (64, 96, 128)", c.head_dim);
+    VGPT_REQUIRE(c.scale > 0.f, VGPT_ERR_INVALID, "vgpt_attn_blockmask_fwd: scale must be positive");
+    VGPT_REQUIRE(c.variant == 0 || c.variant == 1, VGPT_ERR_INVALID,
+                 "vgpt_attn_blockmask_fwd: unknown variant %d", c.variant);
+    const int64_t strides[] = {c.q_sb, c.q_sh, c.q_ss, c.k_sb, c.k_sh, c.k_ss, c.v_sb, c.v_sh, c.v_ss};
     for (int64_t st : strides)
         VGPT_REQUIRE(st % 8 == 0, VGPT_ERR_UNSUPPORTED,
                      "vgpt_attn_blockmask_fwd: q/k/v strides must be multiples of 8 elements");
-    VGPT_REQUIRE(o_sb % 4 == 0 && o_sh % 4 == 0 && o_ss % 4 == 0, VGPT_ERR_UNSUPPORTED,
+    VGPT_REQUIRE(c.o_sb % 4 == 0 && c.o_sh % 4 == 0 && c.o_ss % 4 == 0, VGPT_ERR_UNSUPPORTED,
                  "vgpt_attn_blockmask_fwd: o strides must be multiples of 4 elements");
-    VGPT_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0 && ((uintptr_t)o & 7) == 0,
+    VGPT_REQUIRE((((uintptr_t)c.q | (uintptr_t)c.k | (uintptr_t)c.v) & 15) == 0 && ((uintptr_t)c.o & 7) == 0,
                  VGPT_ERR_UNSUPPORTED, "vgpt_attn_blockmask_fwd: q/k/v must be 16-byte aligned");
-    VGPT_REQUIRE(L < (1 << 24) && B * n_heads * cdiv(L, 128) < (1ll << 31), VGPT_ERR_UNSUPPORTED,
+    VGPT_REQUIRE(c.L < (1 << 24) && c.B * c.n_heads * cdiv(c.L, 128) < (1ll << 31), VGPT_ERR_UNSUPPORTED,
                  "vgpt_attn_blockmask_fwd: problem too large");
-    VGPT_REQUIRE(k_ss > 0 && v_ss > 0 && k_ss < (1 << 24) && v_ss < (1 << 24), VGPT_ERR_UNSUPPORTED,
+    VGPT_REQUIRE(c.k_ss > 0 && c.v_ss > 0 && c.k_ss < (1 << 24) && c.v_ss < (1 << 24), VGPT_ERR_UNSUPPORTED,
                  "vgpt_attn_blockmask_fwd: key/value row strides must be in (0, 2^24) elements");
-    VGPT_REQUIRE(q_start >= 0 && q_start % 128 == 0 && q_start <= L, VGPT_ERR_INVALID,
+    VGPT_REQUIRE(c.q_start >= 0 && c.q_start % 128 == 0 && c.q_start <= c.L, VGPT_ERR_INVALID,
                  "vgpt_attn_blockmask_fwd: q_start must be a multiple of 128 in [0, L]");
-    if (B == 0 || L == 0 || q_start >= L) return VGPT_OK;
+    if (c.B == 0 || c.L == 0 || c.q_start >= c.L) return VGPT_OK;
     if (plan && plan->n_items == 0) return VGPT_OK;
+    AttnLaunch launch_fn = nullptr;
+    if (const int rc = attn_fwd_select(c.head_dim, c.variant, plan ? plan->item_rows : 128, attn_p2_enabled(), &launch_fn)) return rc;
     AttnArgs a;
-    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (bf16*)o;
-    a.bits = bits; a.summary = summary; a.order = order; a.lse = lse;
-    a.B = (int)B; a.L = (int)L; a.n_heads = n_heads; a.kv_group = n_heads / n_kv_heads;
-    a.W = (int)cdiv(L, 32); a.nqb = (int)cdiv(L, 128); a.nkt = (int)cdiv(L, 64); a.qb0 = (int)(q_start / 128);
-    a.q_sb = q_sb; a.q_sh = q_sh; a.q_ss = q_ss; a.k_sb = k_sb; a.k_sh = k_sh; a.k_ss = k_ss;
-    a.v_sb = v_sb; a.v_sh = v_sh; a.v_ss = v_ss; a.o_sb = o_sb; a.o_sh = o_sh; a.o_ss = o_ss;
-    a.scale_log2e = scale * 1.4426950408889634f;
+    a.q = (const bf16*)c.q; a.k = (const bf16*)c.k; a.v = (const bf16*)c.v; a.o = (bf16*)c.o;
+    a.bits = c.bits; a.summary = c.summary; a.order = c.order; a.lse = c.lse;
+    a.B = (int)c.B; a.L = (int)c.L; a.n_heads = c.n_heads; a.kv_group = c.n_heads / c.n_kv_heads;
+    a.W = (int)cdiv(c.L, 32); a.nqb = (int)cdiv(c.L, 128); a.nkt = (int)cdiv(c.L, 64); a.qb0 = (int)(c.q_start / 128);
+    a.q_sb = c.q_sb; a.q_sh = c.q_sh; a.q_ss = c.q_ss; a.k_sb = c.k_sb; a.k_sh = c.k_sh; a.k_ss = c.k_ss;
+    a.v_sb = c.v_sb; a.v_sh = c.v_sh; a.v_ss = c.v_ss; a.o_sb = c.o_sb; a.o_sh = c.o_sh; a.o_ss = c.o_ss;
+    a.scale_log2e = c.scale * 1.4426950408889634f;
     a.items = plan ? plan->items : nullptr;
     a.isum = plan ? plan->isum : nullptr;
     a.iorder = plan ? plan->order : nullptr;
     a.n_items = plan ? (int)plan->n_items : 0;
-    const int64_t n_wg = plan ? plan->n_items * n_heads : (int64_t)(a.nqb - a.qb0) * n_heads * B;
+    const int64_t n_wg = plan ? plan->n_items * c.n_heads : (int64_t)(a.nqb - a.qb0) * c.n_heads * c.B;
     a.trace = n_wg <= g_trace_cap ? g_trace : nullptr;
     a.trace_cap = g_trace_cap;
-    hipStream_t s = (hipStream_t)stream;
-    int rc = VGPT_ERR_UNSUPPORTED;
-#define ATTN_CASE(DD)                                                                     \
-    case DD:                                                                              \
-        rc = variant == 0 ? launch<DD, true>(a, s) : launch<DD, false>(a, s);             \
-        break;
-    if (plan && plan->item_rows == 256) {
-        VGPT_REQUIRE(head_dim == 96 && variant == 0, VGPT_ERR_UNSUPPORTED,
-                     "vgpt_attn_fwd_plan: 256-row items need head_dim 96 (got %d)", head_dim);
-        return launch<96, true, 8>(a, s);
-    }
-    if (head_dim == 96 && variant == 0 && attn_p2_enabled()) return launch<96, true, 4, true>(a, s);
-    switch (head_dim) {
-        ATTN_CASE(64) ATTN_CASE(96) ATTN_CASE(128)
-    }
-#undef ATTN_CASE
-    return rc;
+    return launch_fn(a, (hipStream_t)c.stream);
 }
 
 VGPT_EXPORT int vgpt_attn_blockmask_fwd(const void* q, const void* k, const void* v, void* o,
@@ -880,8 +810,11 @@ VGPT_EXPORT int vgpt_attn_blockmask_fwd(const void* q, const void* k, const void
                                         int64_t k_sh, int64_t k_ss, int64_t v_sb, int64_t v_sh,
                                         int64_t v_ss, int64_t o_sb, int64_t o_sh, int64_t o_ss,
                                         float scale, int variant, void* stream) {
-    return attn_fwd_impl(q, k, v, o, nullptr, 0, bits, summary, nullptr, nullptr, B, L, n_heads, n_kv_heads, head_dim, q_sb, q_sh, q_ss,
-                         k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, scale, variant, stream);
+    AttnCall c = {q, k, v, o, bits, B, L, n_heads, n_kv_heads, head_dim,
+                  q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, scale, stream};
+    c.summary = summary;
+    c.variant = variant;
+    return attn_fwd_impl(c);
 }
 
 VGPT_EXPORT int vgpt_attn_blockmask_fwd_lse(const void* q, const void* k, const void* v, void* o, float* lse,
@@ -895,8 +828,12 @@ VGPT_EXPORT int vgpt_attn_blockmask_fwd_lse(const void* q, const void* k, const 
         vgpt_set_error("vgpt_attn_blockmask_fwd_lse: null lse");
         return VGPT_ERR_INVALID;
     }
-    return attn_fwd_impl(q, k, v, o, lse, 0, bits, summary, order, nullptr, B, L, n_heads, n_kv_heads, head_dim, q_sb, q_sh, q_ss,
-                         k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, scale, 0, stream);
+    AttnCall c = {q, k, v, o, bits, B, L, n_heads, n_kv_heads, head_dim,
+                  q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, scale, stream};
+    c.summary = summary;
+    c.order = order;
+    c.lse = lse;
+    return attn_fwd_impl(c);
 }
 
 VGPT_EXPORT int vgpt_attn_blockmask_fwd_qrange(const void* q, const void* k, const void* v, void* o, int64_t q_start,
@@ -907,8 +844,12 @@ VGPT_EXPORT int vgpt_attn_blockmask_fwd_qrange(const void* q, const void* k, con
                                                int64_t k_sh, int64_t k_ss, int64_t v_sb, int64_t v_sh,
                                                int64_t v_ss, int64_t o_sb, int64_t o_sh, int64_t o_ss,
                                                float scale, void* stream) {
-    return attn_fwd_impl(q, k, v, o, nullptr, q_start, bits, summary, order, nullptr, B, L, n_heads, n_kv_heads, head_dim, q_sb, q_sh,
-                         q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, scale, 0, stream);
+    AttnCall c = {q, k, v, o, bits, B, L, n_heads, n_kv_heads, head_dim,
+                  q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, scale, stream};
+    c.summary = summary;
+    c.order = order;
+    c.q_start = q_start;
+    return attn_fwd_impl(c);
 }
 
 namespace {
@@ -1001,6 +942,9 @@ VGPT_EXPORT int vgpt_attn_fwd_plan(const void* q, const void* k, const void* v, 
     VGPT_REQUIRE(items && item_summary && order, VGPT_ERR_INVALID, "vgpt_attn_fwd_plan: null pointer");
     VGPT_REQUIRE(item_rows == 128 || item_rows == 256, VGPT_ERR_INVALID, "vgpt_attn_fwd_plan: item_rows must be 128 or 256");
     const ItemPlan plan = {items, item_summary, order, n_items, item_rows};
-    return attn_fwd_impl(q, k, v, o, lse, 0, bits, nullptr, nullptr, &plan, B, L, n_heads, n_kv_heads, head_dim, q_sb, q_sh, q_ss,
-                         k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, scale, 0, stream);
+    AttnCall c = {q, k, v, o, bits, B, L, n_heads, n_kv_heads, head_dim,
+                  q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, scale, stream};
+    c.plan = &plan;
+    c.lse = lse;
+    return attn_fwd_impl(c);
 }
