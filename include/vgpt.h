@@ -660,6 +660,46 @@ int64_t vgpt_lora_grad_workspace_bytes(int64_t M, int64_t N, int rp);
 int vgpt_lora_grad(const void* Y, const void* U, float* G, int64_t M, int64_t N, int rp, int64_t ldy, int64_t ldu,
                    int store_transposed, float alpha, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- frame preprocessing (LVM/processor.py:31-35, 39-64 crop_arr, 78-86; LVM/utils.py:47-66 center_crop_arr) ----------------
+ * Decoded uint8 frames -> the (N, 3, h, w) fp32 tensors in [-1, 1] the VAE encoder reads, without leaving the device:
+ * PIL.Image.resize with BOX / BICUBIC, the centre crop, ToTensor + Normalize(0.5, 0.5).  The resampler is Pillow's 8-bit one
+ * restated: integer arithmetic on a coefficient table built in double precision, so results are Pillow's bit for bit.
+ * Frames are (N, H, W, 3) uint8, contiguous, exactly 3 channels (the ABI has no channel argument); any byte alignment.
+ *   One pass along one axis (input length in, output length out, filter support S: BOX 0.5, BICUBIC 2 with a = -0.5):
+ *       scale = in / out, fs = max(scale, 1), sup = S fs, ksize = 2 (int)ceil(sup) + 1, ss = 1 / fs; for output xx:
+ *       center = (xx + 0.5) scale, xmin = max((int)(center - sup + 0.5), 0), xmax = min((int)(center + sup + 0.5), in) - xmin,
+ *       w[x] = f((x + xmin - center + 0.5) ss) for x < xmax, normalised by their sum (added in index order) when it is not 0,
+ *       k[x] = (int)(w[x] 2^22 +- 0.5) truncated toward zero (the sign of w[x] picks +-), k[xmax..ksize-1] = 0;
+ *       out byte = clamp((2^21 + sum_x src[xmin + x] k[x]) >> 22, 0, 255), arithmetic shift on a signed 32-bit sum.
+ *   A resize is the horizontal pass if the width changes, then the vertical pass if the height changes, on the uint8 result
+ *   of the first; a pass whose length does not change is NOT run (the caller skips it).
+ *   vgpt_resample_ksize: host only.  ksize of a pass; sizes < 1 or an unknown filter: VGPT_ERR_INVALID; ksize >
+ *       VGPT_RESAMPLE_MAX_KSIZE: VGPT_ERR_UNSUPPORTED (129 admits a BICUBIC ratio of 32; crop_arr never exceeds 9).
+ *   vgpt_resample_coeffs: host only, writes HOST memory: bounds[2 xx] = xmin, bounds[2 xx + 1] = xmax (2 out words) and
+ *       coeffs (out, ksize).  Same refusals; a NULL pointer: VGPT_ERR_INVALID.
+ *   vgpt_resample_u8: one pass over DEVICE pointers, bounds / coeffs being device copies of the table above for
+ *       (in_w, out_len) when axis = 1 (horizontal: dst is (N, in_h, out_len, 3)) or (in_h, out_len) when axis = 0 (vertical:
+ *       dst is (N, out_len, in_w, 3)).  Table entries are clamped to the image, so a wrong table gives wrong pixels only.
+ *       NULL pointer, another axis, n_frames < 0, a side or ksize < 1, dst == src: VGPT_ERR_INVALID; ksize >
+ *       VGPT_RESAMPLE_MAX_KSIZE or a side > 2^24: VGPT_ERR_UNSUPPORTED; n_frames == 0: VGPT_OK.
+ *   vgpt_u8_to_chw_norm: dst_f32 (N, 3, h, w)[n][c][y][x] = norm(src[n][y0 + y][x0 + x][c]) with norm(b) =
+ *       (fp32(b) / 255.0f - 0.5f) / 0.5f, both divisions correctly rounded (ToTensor + Normalize on the CPU).  A window
+ *       with a negative offset, a side < 1 or an end past H / W: VGPT_ERR_INVALID, naming the values.
+ *   vgpt_resample_u8_v_chw_norm: the vertical pass (in_h -> out_h) writing the window (y0, x0, h, w) of its (out_h, in_w)
+ *       result as normalised planar fp32: bit for bit vgpt_resample_u8(axis 0) followed by vgpt_u8_to_chw_norm, without the
+ *       uint8 image in between and without the rows and columns the crop drops. */
+#define VGPT_FILTER_BOX 0
+#define VGPT_FILTER_BICUBIC 1
+#define VGPT_RESAMPLE_MAX_KSIZE 129
+int vgpt_resample_ksize(int in, int out, int filter);
+int vgpt_resample_coeffs(int in, int out, int filter, int32_t* bounds /* 2*out: xmin, xmax */, int32_t* coeffs /* out*ksize */);
+int vgpt_resample_u8(const void* src, void* dst, const int32_t* bounds, const int32_t* coeffs, int ksize, int n_frames,
+                     int in_h, int in_w, int out_len, int axis, void* stream);
+int vgpt_u8_to_chw_norm(const void* src, float* dst_f32, int n_frames, int H, int W, int y0, int x0, int h, int w,
+                        void* stream);
+int vgpt_resample_u8_v_chw_norm(const void* src, float* dst_f32, const int32_t* bounds, const int32_t* coeffs, int ksize,
+                                int n_frames, int in_h, int in_w, int out_h, int y0, int x0, int h, int w, void* stream);
+
 /* ---- hipGraph helpers (sampler loop under graph capture) ----------------- */
 int vgpt_graph_begin_capture(void* stream);
 int vgpt_graph_end_capture(void* stream, void** graph_exec_out);

@@ -19,6 +19,7 @@ ACT_SILU, ACT_GELU, ACT_GELU_TANH, ACT_NONE = 0, 1, 2, 3
 EPI_NONE, EPI_RESID, EPI_BIAS = 0, 1, 2
 MX8_EPI_NONE, MX8_EPI_RESID, MX8_EPI_ROPE, MX8_EPI_GATED = 0, 1, 2, 3
 PRED_V, PRED_X1 = 0, 1
+FILTER_BOX, FILTER_BICUBIC = 0, 1
 
 _P = c_void_p
 _I64 = c_int64
@@ -140,6 +141,11 @@ SIGNATURES = {
     "vgpt_lora_up_add": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, c_int, _I64, c_int, c_int, c_int, c_int, c_float, _P]),
     "vgpt_lora_grad_workspace_bytes": (_I64, [_I64, _I64, c_int]),
     "vgpt_lora_grad": (c_int, [_P, _P, _P, _I64, _I64, c_int, _I64, _I64, c_int, c_float, _P, _I64, _P]),
+    "vgpt_resample_ksize": (c_int, [c_int, c_int, c_int]),
+    "vgpt_resample_coeffs": (c_int, [c_int, c_int, c_int, _P, _P]),
+    "vgpt_resample_u8": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "vgpt_u8_to_chw_norm": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "vgpt_resample_u8_v_chw_norm": (c_int, [_P, _P, _P, _P] + [c_int] * 9 + [_P]),
     "vgpt_graph_begin_capture": (c_int, [_P]),
     "vgpt_graph_end_capture": (c_int, [_P, POINTER(c_void_p)]),
     "vgpt_graph_launch": (c_int, [_P, _P]),

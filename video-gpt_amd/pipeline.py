@@ -99,6 +99,20 @@ class LVMPipeline:
             return [DiagonalGaussianDistribution(mom[i:i + 1]) for i in range(len(imgs))]
         return [self.vae.encode(t).latent_dist for t in imgs]
 
+    def preprocess_frames(self, frames):
+        """Decoded frames -- an (N, H, W, 3) uint8 GPU tensor or a list of equally sized (H, W, 3) ones, e.g. the
+        `output_type="pt"` frames of an earlier call -- through LVMProcessor.process_frames: the list of (3, h, w) tensors
+        both entry points accept as `input_images`, with no host round trip."""
+        return list(self.processor.process_frames(frames).unbind(0))
+
+    def encode_frames(self, frames, dtype, noise: Optional[List[torch.Tensor]] = None):
+        """Decoded frames -> their latents: preprocess_frames, ONE batched vae_posteriors, then the per-frame vae_encode
+        sampling in the RNG order of the entry points (`noise`: one (1, 4, h/8, w/8) fp32 tensor per frame instead)."""
+        x = self.processor.process_frames(frames)
+        dists = self.vae_posteriors([x[i:i + 1] for i in range(x.shape[0])])
+        return [self.vae_encode(None, dtype, None if noise is None else noise[i].to(self.device), dist=d)
+                for i, d in enumerate(dists)]
+
     def _to_images(self, u8: torch.Tensor, output_type: str):
         if output_type == "pt":
             return [u8[i] for i in range(u8.shape[0])]

@@ -29,9 +29,56 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from ._lib import FILTER_BICUBIC, FILTER_BOX
 from .layout import TokenLayout
 
 PAD, CLEAN, NOISY = 0, 1, 2
+
+
+# ------------------------------------------------------------------------------------------------
+# resize / crop plans of decoded frames (the Pillow calls of crop_arr and center_crop_arr, as data)
+# ------------------------------------------------------------------------------------------------
+
+def _resized(steps, filt, w, h):
+    if w < 1 or h < 1:
+        raise ValueError(f"height and width must be > 0, the plan resizes to {w}x{h}")
+    steps.append((filt, (w, h)))
+    return w, h
+
+
+def crop_arr_plan(width: int, height: int, max_image_size: int):
+    """`LVMProcessor.crop_arr` on a width x height image as a plan: ([(filter, (w, h)), ...], (left, upper, right,
+    lower)) -- the `Image.resize` calls in order (filter = FILTER_BOX | FILTER_BICUBIC) and the crop box on the last size."""
+    w, h = int(width), int(height)
+    if w < 1 or h < 1:
+        raise ValueError(f"height and width must be > 0, got {w}x{h}")
+    steps = []
+    while min(w, h) >= 2 * max_image_size:
+        w, h = _resized(steps, FILTER_BOX, w // 2, h // 2)
+    if max(w, h) > max_image_size:
+        scale = max_image_size / max(w, h)
+        w, h = _resized(steps, FILTER_BICUBIC, round(w * scale), round(h * scale))
+    if min(w, h) < 16:
+        scale = 16 / min(w, h)
+        w, h = _resized(steps, FILTER_BICUBIC, round(w * scale), round(h * scale))
+    y1, x1 = (h % 16) // 2, (w % 16) // 2
+    y2, x2 = h % 16 - y1, w % 16 - x1
+    return steps, (x1, y1, w - x2, h - y2)
+
+
+def center_crop_plan(width: int, height: int, image_size: int):
+    """`center_crop_arr` (LVM/utils.py:47-66) as a plan of the same form: BOX halvings while the short side is at least
+    2 * image_size, a BICUBIC resize that brings the short side to image_size, the centred image_size square."""
+    w, h = int(width), int(height)
+    if w < 1 or h < 1:
+        raise ValueError(f"height and width must be > 0, got {w}x{h}")
+    steps = []
+    while min(w, h) >= 2 * image_size:
+        w, h = _resized(steps, FILTER_BOX, w // 2, h // 2)
+    scale = image_size / min(w, h)
+    w, h = _resized(steps, FILTER_BICUBIC, round(w * scale), round(h * scale))
+    cy, cx = (h - image_size) // 2, (w - image_size) // 2
+    return steps, (cx, cy, cx + image_size, cy + image_size)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -436,6 +483,42 @@ class LVMProcessor:
         arr = self.crop_arr(image)
         t = torch.from_numpy(np.ascontiguousarray(arr)).permute(2, 0, 1).float().div(255.0)
         return (t - 0.5) / 0.5
+
+    # -- decoded frames on the device --
+    @staticmethod
+    def _frames_tensor(frames) -> torch.Tensor:
+        if not torch.is_tensor(frames):
+            frames = list(frames)
+            if not frames or any(not torch.is_tensor(f) or f.shape != frames[0].shape for f in frames):
+                raise ValueError("frames must be an (N, H, W, 3) uint8 tensor or a non-empty list of equally sized (H, W, 3) ones")
+            frames = torch.stack(frames)
+        if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+            raise ValueError(f"frames must be (N, H, W, 3) uint8, got {tuple(frames.shape)} {frames.dtype}")
+        return frames
+
+    @staticmethod
+    def _run_plan(frames: torch.Tensor, steps, box) -> torch.Tensor:
+        """All resizes but the last as uint8, the last one fused with the crop and the normalisation."""
+        from . import ops_image
+        for filt, size in steps[:-1]:
+            frames = ops_image.resample_u8(frames, size, filt)
+        if steps:
+            return ops_image.resample_chw_norm(frames, steps[-1][1], steps[-1][0], box)
+        return ops_image.u8_to_chw_norm(frames, box)
+
+    def process_frames(self, frames) -> torch.Tensor:
+        """`process_image` on decoded frames without leaving the device: an (N, H, W, 3) uint8 GPU tensor (or a list of
+        equally sized (H, W, 3) ones) -> (N, 3, h, w) fp32 in [-1, 1], bit for bit torch.stack of process_image(PIL frame)."""
+        frames = self._frames_tensor(frames)
+        steps, box = crop_arr_plan(frames.shape[2], frames.shape[1], self.max_image_size)
+        return self._run_plan(frames, steps, box)
+
+    def center_crop_frames(self, frames, image_size: int) -> torch.Tensor:
+        """`center_crop_arr(frame, image_size)` (LVM/utils.py:47-66) followed by ToTensor + Normalize(0.5, 0.5), on the
+        device: (N, 3, image_size, image_size) fp32 in [-1, 1]."""
+        frames = self._frames_tensor(frames)
+        steps, box = center_crop_plan(frames.shape[2], frames.shape[1], image_size)
+        return self._run_plan(frames, steps, box)
 
     def _chunks(self, text: str):
         chunks = [list(self.text_tokenizer(c).input_ids) for c in self._TAG.split(text)]
