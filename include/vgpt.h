@@ -528,6 +528,16 @@ int vgpt_attn_blockmask_bwd(const void* q, const void* k, const void* v, const v
                             const float* lse, float* delta_ws, void* dq, void* dk, void* dv, const uint32_t* bits,
                             const uint8_t* summary, int64_t B, int64_t L, int n_heads, int n_kv_heads, int head_dim,
                             const int64_t* strides, float scale, void* stream);
+/* The same backward for every head dim of vgpt_attn_bwd_supported() (64, 96, 128): torch.autograd through
+ * F.scaled_dot_product_attention, LVM/transform/sdpa_transform.py:78-86,152.  Same parameters, stride, alignment and
+ * null rules as vgpt_attn_blockmask_bwd (which stays the head_dim 96 entry); refusals name the offending value.
+ * head_dim 96 runs the kernels of vgpt_attn_blockmask_bwd, bit for bit. */
+int vgpt_attn_blockmask_bwd_hd(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                               const float* lse, float* delta_ws, void* dq, void* dk, void* dv, const uint32_t* bits,
+                               const uint8_t* summary, int64_t B, int64_t L, int n_heads, int n_kv_heads, int head_dim,
+                               const int64_t* strides, float scale, void* stream);
+/* 1 if vgpt_attn_blockmask_bwd_hd has kernels for this head dim, else 0. */
+int vgpt_attn_bwd_supported(int head_dim);
 
 /* (R, C) bf16 row stride ld_in -> (C, Rp) bf16, columns r >= R zero-filled (operands of the backward NT GEMMs). */
 int vgpt_transpose_pad_bf16(const void* in, void* out, int64_t R, int64_t C, int64_t Rp, int64_t ld_in, void* stream);

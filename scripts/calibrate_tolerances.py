@@ -11,6 +11,8 @@ tests/smoke_case.py::tol().  CPU only, about a minute; re-run after changing a t
 
   python scripts/calibrate_tolerances.py            # tiny cases (what the tests use)
   python scripts/calibrate_tolerances.py --fullwidth   # + one full-width layer (H 3072) over a 516-token clip, ~2 min
+  python scripts/calibrate_tolerances.py --head-dims   # only the head-dim 64 / 128 training configs of
+                                                       # tests/head_dim_cases.py -> tolerance_calibration_head_dims.json
 """
 import argparse
 import json
@@ -148,13 +150,35 @@ def fullwidth_stage1():
     return {"fullwidth_stage1_loss": [rel(runs["bf16"][0], runs["f32"][0])], "fullwidth_stage1_param_grads": [max(per.values())]}
 
 
+def head_dims():
+    """Loss and gradients of the stage-1 case on the head-dim 64 / 128 configs of tests/head_dim_cases.py (same seeds and
+    same measurement as the tiny config's), written to tests/golden/tolerance_calibration_head_dims.json."""
+    from tests import head_dim_cases as HC
+    q = {}
+    for hd, cfg in HC.CONFIGS.items():
+        for k, v in loss_and_grads(cfg, (3, 4, 5)).items():
+            q[f"hd{hd}.{k}"] = {"stock_bf16_rel_l2_max": round(max(v), 6), "stock_bf16_rel_l2_mean": round(sum(v) / len(v), 6),
+                                "samples": len(v), "tolerance": round(2 * max(v), 6)}
+    doc = {"what": "rel-L2 of oracle/restate.py run with torch's stock CPU bf16 ops against its fp32 self on the stage-1 case "
+                   "of the head-dim 64 (4 heads / 2 kv heads) and 128 (2 heads / 1 kv head) configs, hidden size 256; "
+                   "tolerance = 2 x the largest value (SURVEY.md section 8d)",
+           "generated_by": "scripts/calibrate_tolerances.py --head-dims", "torch": torch.__version__, "quantities": q}
+    json.dump(doc, open(HC.PATH, "w"), indent=1)
+    for k, v in q.items():
+        print(f"{k:26s} stock bf16 max {v['stock_bf16_rel_l2_max']:.3e}  mean {v['stock_bf16_rel_l2_mean']:.3e}  -> tolerance {v['tolerance']:.3e}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fullwidth", action="store_true")
     ap.add_argument("--fullwidth-stage1", action="store_true", help="only the cfg-3 full-width stage-1 quantities (slow)")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "tolerance_calibration.json"))
+    ap.add_argument("--head-dims", action="store_true",
+                    help="only loss / gradients of the head-dim 64 and 128 training configs, to their own file")
     args = ap.parse_args()
     torch.manual_seed(0)
+    if args.head_dims:
+        return head_dims()
     cfg = R.TINY
     seeds = (0, 1, 2)
     meas = {}

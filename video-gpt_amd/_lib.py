@@ -105,6 +105,9 @@ SIGNATURES = {
         c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, c_int, c_int, c_int] + [_I64] * 12 + [c_float, _P]),
     "vgpt_attn_blockmask_bwd": (
         c_int, [_P] * 12 + [_I64, _I64, c_int, c_int, c_int, _P, c_float, _P]),
+    "vgpt_attn_blockmask_bwd_hd": (
+        c_int, [_P] * 12 + [_I64, _I64, c_int, c_int, c_int, _P, c_float, _P]),
+    "vgpt_attn_bwd_supported": (c_int, [c_int]),
     "vgpt_transpose_pad_bf16": (c_int, [_P, _P, _I64, _I64, _I64, _I64, _P]),
     "vgpt_silu_mul_fwd": (c_int, [_P, _P, _I64, _I64, c_int, _P]),
     "vgpt_silu_mul_bwd": (c_int, [_P, _P, _P, _I64, _I64, c_int, _P]),

@@ -1,4 +1,4 @@
-// Block-masked flash attention BACKWARD for gfx950 (head_dim 96, bf16 in/out, fp32 softmax math).
+// Block-masked flash attention BACKWARD for gfx950 (head_dim 64 / 96 / 128, bf16 in/out, fp32 softmax math).
 //
 // The reference obtains these gradients from torch.autograd through F.scaled_dot_product_attention
 // (LVM/transform/sdpa_transform.py:78-86,152 inside accelerator.backward, train_x1_stage1_noiseinput.py:380).
@@ -13,16 +13,50 @@
 //   attn_bwd_dkv_kernel — a wave owns 32 KEYS and walks the query tiles: S = Q K^T, dP = dO V^T (queries on
 //                         accumulator rows, the key on the lane), dV^T += dO^T P, dK^T += Q^T dS with the
 //                         transposed operands again from ds_read_b64_tr_b16 on the [row][d] LDS images.
-// Every LDS image is a contiguous [row][192 B] tile filled by LDS-DMA with the chunk XOR-swizzle
-// (chunk ^= (row>>2)&3) that makes ds_read_b128 row reads conflict-free and leaves the 64-byte windows of
-// the transposed reads intact (the XOR is constant over the 4 rows of a transposed-read block).
+// Every LDS image is a contiguous [row][2 D bytes] tile filled by LDS-DMA (1-KiB pieces, so rows cannot be padded) with
+// a chunk XOR-swizzle applied on the DMA source address and on every read.  The swizzle per head dim (swz<D>):
+//   D  96 (192-B rows): chunk ^= (row>>2)&3.  Four consecutive rows start 48 banks apart, so the XOR only has to
+//          separate the 4-row groups; it is constant over the 4 rows of a transposed-read block.
+//   D  64 (128-B rows): chunk ^= ((row>>1)&1)<<2 | (row>>2)&3.  Two rows fill the 64-bank window; with the 96 XOR rows
+//          r and r+2 of a block share their banks (2-way on both kinds of read).
+//   D 128 (256-B rows): chunk ^= (row&3)<<2 | (row>>2)&3.  Every row starts at bank 0; with the 96 XOR the four rows
+//          of a block share their banks (4-way on both kinds of read).
+// An XOR that is constant over the 4 rows of a ds_read_b64_tr_b16 block cannot do better than that at 128- and 256-byte
+// rows: rows r .. r+3 then keep the same chunk, hence the same banks.  What tr_frag needs is weaker: the 64-byte window
+// (4 chunks) that a 16-lane group reads from a row must stay one aligned 64-byte window, and every lane forms its address
+// from its own row.  The row-in-block bits therefore enter the XOR shifted by 2 (they move whole 64-byte windows), the
+// block bits (row>>2)&3 permute the chunks inside a window as before.  By the bank rule (bank = (addr/4) mod 64; 16-lane
+// groups {0-3,12-15,20-27},.. for ds_read_b128, 32-lane halves for the transposed read) NO conflict remains at any of
+// the three head dims, on the row reads and on the transposed reads alike; SQ_LDS_BANK_CONFLICT reads 0 in all six
+// kernels at the cfg-3 mask (profiles/attn_bwd_head_dims_pmc.log).
+//
+// Registers: the dQ kernel keeps two waves per SIMD at every head dim.  At D 128 the budget (64 Q,dO + 64 dQ + 64 K,V
+// rows + 32 K^T + 32 S,dP) does not fit 256, so that instantiation shortens the live ranges the way the dK/dV kernel
+// does: S from the K rows, then dP from the V rows (half a row of fragments in flight), then the K^T fragments one
+// 32-wide d tile at a time (237 VGPRs, no scratch).  The D 64 and D 96 instantiations keep the original order; the 96
+// instantiation is the kernel this file held before it took D as a template parameter.
 #include "common.h"
 
 namespace {
 
-constexpr int D = 96, KS = D / 16, DT = D / 32, CHUNKS = D / 8, ROWB = D * 2;
-constexpr int TILE_BYTES = 64 * ROWB;  // 12 KiB image of 64 rows
-constexpr int PIECES = TILE_BYTES / 1024 / 4;
+template <int D>
+struct Dims {
+    static_assert(D == 64 || D == 96 || D == 128, "head dim");
+    static constexpr int KS = D / 16, DT = D / 32, CHUNKS = D / 8, ROWB = D * 2;
+    static constexpr int TILE_BYTES = 64 * ROWB;  // 8 / 12 / 16 KiB image of 64 rows
+    static constexpr int PIECES = TILE_BYTES / 1024 / 4;
+    static constexpr int LDS_DQ = 2 * 2 * TILE_BYTES + 4096 + 2048;             // 38 / 54 / 70 KiB
+    static constexpr int LDS_DKV = 2 * (2 * TILE_BYTES + 512 + 1024) + 4096;   // 39 / 55 / 71 KiB
+    static constexpr bool SPLIT_DQ = D == 128;  // dQ kernel: S from K rows, then dP from V rows (register budget)
+};
+
+// chunk XOR of image row `row` (file header)
+template <int D>
+__device__ __forceinline__ int swz(int row) {
+    if constexpr (D == 64) return (((row >> 1) & 1) << 2) | ((row >> 2) & 3);
+    else if constexpr (D == 128) return ((row & 3) << 2) | ((row >> 2) & 3);
+    else return (row >> 2) & 3;
+}
 
 struct BwdArgs {
     const bf16 *q, *k, *v, *o, *dout;
@@ -61,19 +95,22 @@ __device__ __forceinline__ void tile_sync() {
 }
 constexpr int LIST_MAX = 1023;  // active tiles per list chunk (4 KiB of LDS)
 
-// row read of a swizzled [row][192 B] image: lane (r = row, h) gets elements [16s + 8h, +8)
+// row read of a swizzled [row][2 D bytes] image: lane (r = row, h) gets elements [16s + 8h, +8)
+template <int D>
 __device__ __forceinline__ bf16x8 row_frag(const char* img, int row, int s, int h) {
-    const int kc = (2 * s + h) ^ ((row >> 2) & 3);
-    return *reinterpret_cast<const bf16x8*>(img + row * ROWB + kc * 16);
+    const int kc = (2 * s + h) ^ swz<D>(row);
+    return *reinterpret_cast<const bf16x8*>(img + row * Dims<D>::ROWB + kc * 16);
 }
 
 // transposed read: A operand of a 32x32x16 MFMA whose rows are d (32-wide tile dt) and whose k index runs
 // over 16 image rows starting at row16 (+4h, +8 for the upper half): element j <-> row row16 + 8(j>>2) + 4h + (j&3)
+template <int D>
 __device__ __forceinline__ bf16x8 tr_frag(const char* img, int row16, int dt, int lane) {
+    constexpr int ROWB = Dims<D>::ROWB;
     const int h = lane >> 5, li = lane & 15;
     const int row = row16 + 4 * h + (li >> 2);
     const int dcol = dt * 32 + ((lane >> 4) & 1) * 16 + 4 * (li & 3);  // first of 4 consecutive d
-    const int f0 = (row >> 2) & 3, f1 = ((row + 8) >> 2) & 3;
+    const int f0 = swz<D>(row), f1 = swz<D>(row + 8);
     const char* p0 = img + row * ROWB + (((dcol >> 3) ^ f0) * 16) + (dcol & 4) * 2;
     const char* p1 = img + (row + 8) * ROWB + (((dcol >> 3) ^ f1) * 16) + (dcol & 4) * 2;
     bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p0);
@@ -89,14 +126,16 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& x, int half) {
 }
 
 // delta[b][h][q] = sum_d dO[q][d] * O[q][d]
+template <int D>
 __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16* __restrict__ o, const bf16* __restrict__ dout,
                                                          float* __restrict__ delta, int B, int L, int n_heads,
                                                          int64_t o_sb, int64_t o_sh, int64_t o_ss, int64_t do_sb,
                                                          int64_t do_sh, int64_t do_ss) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)B * n_heads * L) return;
-    // head fastest: the 64 lanes of a wave read 64 consecutive 192-byte head slices (two whole token rows of the
-    // (B, L, heads*d) layout) instead of 64 slices 6 KB apart
+    // head fastest: the 64 lanes of a wave read 64 consecutive head slices (192 bytes at D 96: two whole token rows of
+    // the (B, L, heads*d) layout) instead of 64 slices 6 KB apart
+    constexpr int CHUNKS = Dims<D>::CHUNKS;
     const int hd = (int)(idx % n_heads);
     const int q = (int)((idx / n_heads) % L);
     const int b = (int)(idx / ((int64_t)L * n_heads));
@@ -116,7 +155,10 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16* __restrict_
 // ------------------------------------------------------------------------------------------------------
 // dQ: block = 4 waves = 128 query rows of one (batch, head); K/V tiles of 64 keys double-buffered in LDS
 // ------------------------------------------------------------------------------------------------------
+template <int D>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(BwdArgs a) {
+    constexpr int KS = Dims<D>::KS, DT = Dims<D>::DT, CHUNKS = Dims<D>::CHUNKS, TILE_BYTES = Dims<D>::TILE_BYTES;
+    constexpr int PIECES = Dims<D>::PIECES;
     constexpr int STAGE = 2 * TILE_BYTES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -158,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(BwdArgs a) {
     for (int j = 0; j < PIECES; ++j) {
         const int unit = (wave * PIECES + j) * 64 + lane;
         g_key[j] = unit / CHUNKS;
-        g_chunk[j] = (unit % CHUNKS) ^ ((g_key[j] >> 2) & 3);
+        g_chunk[j] = (unit % CHUNKS) ^ swz<D>(g_key[j]);
     }
     const uint32_t lds_base =
         __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
@@ -228,26 +270,57 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(BwdArgs a) {
                 // the two 32-key halves of the tile are processed one after the other (register budget: 2 waves/SIMD)
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb) {
-                    bf16x8 Kf[KS], Vf[KS];
-#pragma unroll
-                    for (int s = 0; s < KS; ++s) {
-                        Kf[s] = row_frag(sk, kb * 32 + r, s, h);
-                        Vf[s] = row_frag(sv, kb * 32 + r, s, h);
-                    }
-                    // K^T fragments for dQ^T += K^T dS^T (independent of the element-wise math below)
-                    bf16x8 Kt[DT][2];
-#pragma unroll
-                    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                        for (int t = 0; t < 2; ++t) Kt[dt][t] = tr_frag(sk, kb * 32 + t * 16, dt, lane);
-                    __builtin_amdgcn_sched_barrier(0);
+                    int ro = r, lo = lane;
                     f32x16 S, dP;
+                    bf16x8 Kt[DT][2];  // K^T fragments for dQ^T += K^T dS^T (independent of the element-wise math below)
+                    if constexpr (!Dims<D>::SPLIT_DQ) {
+                        bf16x8 Kf[KS], Vf[KS];
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) { S[i] = 0.f; dP[i] = 0.f; }
+                        for (int s = 0; s < KS; ++s) {
+                            Kf[s] = row_frag<D>(sk, kb * 32 + r, s, h);
+                            Vf[s] = row_frag<D>(sv, kb * 32 + r, s, h);
+                        }
 #pragma unroll
-                    for (int s = 0; s < KS; ++s) {
-                        S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Kf[s], Qf[s], S, 0, 0, 0);
-                        dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Vf[s], dOf[s], dP, 0, 0, 0);
+                        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+                            for (int t = 0; t < 2; ++t) Kt[dt][t] = tr_frag<D>(sk, kb * 32 + t * 16, dt, lane);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) { S[i] = 0.f; dP[i] = 0.f; }
+#pragma unroll
+                        for (int s = 0; s < KS; ++s) {
+                            S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Kf[s], Qf[s], S, 0, 0, 0);
+                            dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Vf[s], dOf[s], dP, 0, 0, 0);
+                        }
+                    } else {
+                        // one row-fragment set live at a time: S from the K rows, dP from the V rows; K^T per d tile below
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) { S[i] = 0.f; dP[i] = 0.f; }
+                        // the swizzled LDS addresses differ per slice by an XOR, not by an immediate offset: hipcc would hoist
+                        // all of them out of the tile loop (about 20 registers live across it, spilled); made opaque here,
+                        // the lane's row and lane index are recombined per read instead, a few VALU beside the MFMAs
+                        asm volatile("" : "+v"(ro), "+v"(lo));
+                        constexpr int HS = KS / 2;  // half a row (four 16-element slices) in flight at a time
+#pragma unroll
+                        for (int s0 = 0; s0 < KS; s0 += HS) {
+                            bf16x8 Kf[HS];
+#pragma unroll
+                            for (int s = 0; s < HS; ++s) Kf[s] = row_frag<D>(sk, kb * 32 + ro, s0 + s, h);
+#pragma unroll
+                            for (int s = 0; s < HS; ++s)
+                                S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Kf[s], Qf[s0 + s], S, 0, 0, 0);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+#pragma unroll
+                        for (int s0 = 0; s0 < KS; s0 += HS) {
+                            bf16x8 Vf[HS];
+#pragma unroll
+                            for (int s = 0; s < HS; ++s) Vf[s] = row_frag<D>(sv, kb * 32 + ro, s0 + s, h);
+#pragma unroll
+                            for (int s = 0; s < HS; ++s)
+                                dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Vf[s], dOf[s0 + s], dP, 0, 0, 0);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
                     }
                     // dS^T / scale = P^T o (dP^T - delta), P^T = exp2(c S^T - LSE); masked keys -> 0
                     const uint32_t w = (kb ? mw1 : mw0) >> (4 * h);
@@ -267,10 +340,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(BwdArgs a) {
 #pragma unroll
                     for (int t = 0; t < 2; ++t) dSf[t] = pack8(S, t);
 #pragma unroll
-                    for (int dt = 0; dt < DT; ++dt)
+                    for (int dt = 0; dt < DT; ++dt) {
+                        if constexpr (Dims<D>::SPLIT_DQ) {  // K^T of one 32-wide d tile at a time
+#pragma unroll
+                            for (int t = 0; t < 2; ++t) Kt[dt][t] = tr_frag<D>(sk, kb * 32 + t * 16, dt, lo);
+                        }
 #pragma unroll
                         for (int t = 0; t < 2; ++t)
                             dQ[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Kt[dt][t], dSf[t], dQ[dt], 0, 0, 0);
+                        if constexpr (Dims<D>::SPLIT_DQ) __builtin_amdgcn_sched_barrier(0);  // keeps the K^T reads from piling up
+                    }
                 }
             }
             e_cur = e_nxt;
@@ -295,9 +374,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(BwdArgs a) {
 // ------------------------------------------------------------------------------------------------------
 // dK, dV: block = 4 waves = 128 keys of one (batch, kv head); Q/dO tiles of 64 query rows in LDS
 // ------------------------------------------------------------------------------------------------------
-// Both gradients in one launch need ~380 VGPRs (one wave per SIMD); one launch per gradient at two waves per SIMD, each
+// Both gradients in one launch need ~380 VGPRs at D 96 (one wave per SIMD); one launch per gradient at two waves per SIMD, each
 // recomputing S = Q K^T, measured slower (stage-1 attention backward).
+template <int D>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(BwdArgs a) {
+    constexpr int KS = Dims<D>::KS, DT = Dims<D>::DT, CHUNKS = Dims<D>::CHUNKS, TILE_BYTES = Dims<D>::TILE_BYTES;
+    constexpr int PIECES = Dims<D>::PIECES;
     // stage: Q image | dO image | lse[64] | delta[64] | mask words [64][4]
     constexpr int STAT_OFF = 2 * TILE_BYTES, MASK_OFF = STAT_OFF + 512, STAGE = MASK_OFF + 1024;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -333,7 +415,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(BwdArgs a) {
     for (int j = 0; j < PIECES; ++j) {
         const int unit = (wave * PIECES + j) * 64 + lane;
         g_row[j] = unit / CHUNKS;
-        g_chunk[j] = (unit % CHUNKS) ^ ((g_row[j] >> 2) & 3);
+        g_chunk[j] = (unit % CHUNKS) ^ swz<D>(g_row[j]);
     }
     const int nqt = (a.L + 63) / 64;
     const uint32_t lds_base =
@@ -423,14 +505,14 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(BwdArgs a) {
                 {   // S = Q K^T, then dP = dO V^T: one row-fragment set live at a time (register budget)
                     bf16x8 Qr[KS];
 #pragma unroll
-                    for (int s = 0; s < KS; ++s) Qr[s] = row_frag(sq, qh * 32 + r, s, h);
+                    for (int s = 0; s < KS; ++s) Qr[s] = row_frag<D>(sq, qh * 32 + r, s, h);
 #pragma unroll
                     for (int s = 0; s < KS; ++s) S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Qr[s], Kf[s], S, 0, 0, 0);
                 }
                 {   // dP = dO V^T (the scope ends dOr's live range)
                     bf16x8 dOr[KS];
 #pragma unroll
-                    for (int s = 0; s < KS; ++s) dOr[s] = row_frag(sdo, qh * 32 + r, s, h);
+                    for (int s = 0; s < KS; ++s) dOr[s] = row_frag<D>(sdo, qh * 32 + r, s, h);
 #pragma unroll
                     for (int s = 0; s < KS; ++s) dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dOr[s], Vf[s], dP, 0, 0, 0);
                 }
@@ -439,7 +521,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(BwdArgs a) {
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
-                    for (int t = 0; t < 2; ++t) dOt[dt][t] = tr_frag(sdo, qh * 32 + t * 16, dt, lane);
+                    for (int t = 0; t < 2; ++t) dOt[dt][t] = tr_frag<D>(sdo, qh * 32 + t * 16, dt, lane);
                 __builtin_amdgcn_sched_barrier(0);
                 // accumulator register i holds query row qh*32 + 8 (i>>2) + 4h + (i&3): the row statistics of four
                 // consecutive registers are one 16-byte LDS read
@@ -502,7 +584,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(BwdArgs a) {
                     for (int dt = 0; dt < DT; ++dt) {
                         bf16x8 Qt[2];
 #pragma unroll
-                        for (int t = 0; t < 2; ++t) Qt[t] = tr_frag(sq, qh * 32 + t * 16, dt, lane);
+                        for (int t = 0; t < 2; ++t) Qt[t] = tr_frag<D>(sq, qh * 32 + t * 16, dt, lane);
 #pragma unroll
                         for (int t = 0; t < 2; ++t)
                             dK[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Qt[t], dSf[t], dK[dt], 0, 0, 0);
@@ -534,6 +616,49 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(BwdArgs a) {
     }
 }
 
+// launches of one head dim; the dynamic-LDS limits are raised once per instantiation
+template <int D>
+int launch_bwd(const char* name, const BwdArgs& a, float* delta_ws, int64_t B, int64_t L, int n_heads, int n_kv_heads,
+               hipStream_t st) {
+    static bool attr_set = false;
+    constexpr int lds_dq = Dims<D>::LDS_DQ, lds_dkv = Dims<D>::LDS_DKV;
+    if (!attr_set) {
+        hipError_t e1 = hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dq);
+        hipError_t e2 = hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dkv);
+        if (e1 != hipSuccess || e2 != hipSuccess) {
+            vgpt_set_error("%s: hipFuncSetAttribute failed", name);
+            return VGPT_ERR_HIP;
+        }
+        attr_set = true;
+    }
+    const int64_t nstat = B * n_heads * L;
+    hipLaunchKernelGGL(attn_delta_kernel<D>, dim3((unsigned)cdiv(nstat, 256)), dim3(256), 0, st, a.o, a.dout, delta_ws, a.B,
+                       a.L, n_heads, a.o_sb, a.o_sh, a.o_ss, a.do_sb, a.do_sh, a.do_ss);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<D>, dim3(a.nqb * n_heads * a.B), dim3(256), lds_dq, st, a);
+    const dim3 grid_kv((unsigned)(cdiv(L, 128) * n_kv_heads * B));
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<D>, grid_kv, dim3(256), lds_dkv, st, a);
+    VGPT_CHECK_LAUNCH(name);
+    return VGPT_OK;
+}
+
+BwdArgs make_args(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                  float* delta_ws, void* dq, void* dk, void* dv, const uint32_t* bits, const uint8_t* summary, int64_t B,
+                  int64_t L, int n_heads, int n_kv_heads, const int64_t* strides, float scale) {
+    BwdArgs a;
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)o; a.dout = (const bf16*)dout;
+    a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.lse = lse; a.delta = delta_ws; a.bits = bits;
+    a.summary = summary;
+    a.B = (int)B; a.L = (int)L; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.kv_group = n_heads / n_kv_heads;
+    a.W = (int)cdiv(L, 32); a.nqb = (int)cdiv(L, 128); a.nkt = (int)cdiv(L, 64);
+    const int64_t* s = strides;
+    a.q_sb = s[0]; a.q_sh = s[1]; a.q_ss = s[2]; a.k_sb = s[3]; a.k_sh = s[4]; a.k_ss = s[5];
+    a.v_sb = s[6]; a.v_sh = s[7]; a.v_ss = s[8]; a.o_sb = s[9]; a.o_sh = s[10]; a.o_ss = s[11];
+    a.do_sb = s[12]; a.do_sh = s[13]; a.do_ss = s[14]; a.dq_sb = s[15]; a.dq_sh = s[16]; a.dq_ss = s[17];
+    a.dk_sb = s[18]; a.dk_sh = s[19]; a.dk_ss = s[20]; a.dv_sb = s[21]; a.dv_sh = s[22]; a.dv_ss = s[23];
+    a.scale = scale; a.scale_log2e = scale * 1.4426950408889634f;
+    return a;
+}
+
 }  // namespace
 
 VGPT_EXPORT int vgpt_attn_blockmask_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,
@@ -549,36 +674,38 @@ VGPT_EXPORT int vgpt_attn_blockmask_bwd(const void* q, const void* k, const void
         VGPT_REQUIRE(strides[i] % (i < 15 ? 8 : 4) == 0, VGPT_ERR_UNSUPPORTED,
                      "vgpt_attn_blockmask_bwd: strides must be multiples of 8 (inputs) / 4 (outputs) elements");
     if (B == 0 || L == 0) return VGPT_OK;
-    BwdArgs a;
-    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)o; a.dout = (const bf16*)dout;
-    a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.lse = lse; a.delta = delta_ws; a.bits = bits;
-    a.summary = summary;
-    a.B = (int)B; a.L = (int)L; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.kv_group = n_heads / n_kv_heads;
-    a.W = (int)cdiv(L, 32); a.nqb = (int)cdiv(L, 128); a.nkt = (int)cdiv(L, 64);
-    const int64_t* s = strides;
-    a.q_sb = s[0]; a.q_sh = s[1]; a.q_ss = s[2]; a.k_sb = s[3]; a.k_sh = s[4]; a.k_ss = s[5];
-    a.v_sb = s[6]; a.v_sh = s[7]; a.v_ss = s[8]; a.o_sb = s[9]; a.o_sh = s[10]; a.o_ss = s[11];
-    a.do_sb = s[12]; a.do_sh = s[13]; a.do_ss = s[14]; a.dq_sb = s[15]; a.dq_sh = s[16]; a.dq_ss = s[17];
-    a.dk_sb = s[18]; a.dk_sh = s[19]; a.dk_ss = s[20]; a.dv_sb = s[21]; a.dv_sh = s[22]; a.dv_ss = s[23];
-    a.scale = scale; a.scale_log2e = scale * 1.4426950408889634f;
+    const BwdArgs a = make_args(q, k, v, o, dout, lse, delta_ws, dq, dk, dv, bits, summary, B, L, n_heads, n_kv_heads,
+                                strides, scale);
+    return launch_bwd<96>("vgpt_attn_blockmask_bwd", a, delta_ws, B, L, n_heads, n_kv_heads, (hipStream_t)stream);
+}
+
+VGPT_EXPORT int vgpt_attn_bwd_supported(int head_dim) { return head_dim == 64 || head_dim == 96 || head_dim == 128; }
+
+// The same backward for every head dim of vgpt_attn_bwd_supported (vgpt_attn_blockmask_bwd stays the 96-only entry).
+VGPT_EXPORT int vgpt_attn_blockmask_bwd_hd(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                           const float* lse, float* delta_ws, void* dq, void* dk, void* dv,
+                                           const uint32_t* bits, const uint8_t* summary, int64_t B, int64_t L,
+                                           int n_heads, int n_kv_heads, int head_dim, const int64_t* strides, float scale,
+                                           void* stream) {
+    static const char* const names[8] = {"q", "k", "v", "o", "dout", "dq", "dk", "dv"};
+    VGPT_REQUIRE(q && k && v && o && dout && lse && delta_ws && dq && dk && dv && bits && summary && strides,
+                 VGPT_ERR_INVALID, "vgpt_attn_blockmask_bwd_hd: null pointer");
+    VGPT_REQUIRE(vgpt_attn_bwd_supported(head_dim), VGPT_ERR_UNSUPPORTED,
+                 "vgpt_attn_blockmask_bwd_hd: head_dim %d unsupported (64, 96, 128)", head_dim);
+    VGPT_REQUIRE(B >= 0 && L >= 0 && n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0 && scale > 0.f,
+                 VGPT_ERR_INVALID, "vgpt_attn_blockmask_bwd_hd: bad shape (B %lld, L %lld, n_heads %d, n_kv_heads %d, scale %g)",
+                 (long long)B, (long long)L, n_heads, n_kv_heads, (double)scale);
+    for (int i = 0; i < 24; ++i)
+        VGPT_REQUIRE(strides[i] % (i < 15 ? 8 : 4) == 0, VGPT_ERR_UNSUPPORTED,
+                     "vgpt_attn_blockmask_bwd_hd: stride %d (%s, %s) is %lld: strides must be multiples of 8 (inputs) / 4 "
+                     "(outputs) elements",
+                     i, names[i / 3], i % 3 == 0 ? "batch" : i % 3 == 1 ? "head" : "seq", (long long)strides[i]);
+    if (B == 0 || L == 0) return VGPT_OK;
+    const BwdArgs a = make_args(q, k, v, o, dout, lse, delta_ws, dq, dk, dv, bits, summary, B, L, n_heads, n_kv_heads,
+                                strides, scale);
+    const char* name = "vgpt_attn_blockmask_bwd_hd";
     hipStream_t st = (hipStream_t)stream;
-    static bool attr_set = false;
-    constexpr int lds_dq = 2 * 2 * TILE_BYTES + 4096 + 2048, lds_dkv = 2 * (2 * TILE_BYTES + 512 + 1024) + 4096;
-    if (!attr_set) {
-        hipError_t e1 = hipFuncSetAttribute((const void*)attn_bwd_dq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dq);
-        hipError_t e2 = hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dkv);
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-            vgpt_set_error("vgpt_attn_blockmask_bwd: hipFuncSetAttribute failed");
-            return VGPT_ERR_HIP;
-        }
-        attr_set = true;
-    }
-    const int64_t nstat = B * n_heads * L;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)cdiv(nstat, 256)), dim3(256), 0, st, a.o, a.dout, delta_ws, a.B,
-                       a.L, n_heads, a.o_sb, a.o_sh, a.o_ss, a.do_sb, a.do_sh, a.do_ss);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(a.nqb * n_heads * a.B), dim3(256), lds_dq, st, a);
-    const dim3 grid_kv((unsigned)(cdiv(L, 128) * n_kv_heads * B));
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid_kv, dim3(256), lds_dkv, st, a);
-    VGPT_CHECK_LAUNCH("vgpt_attn_blockmask_bwd");
-    return VGPT_OK;
+    if (head_dim == 64) return launch_bwd<64>(name, a, delta_ws, B, L, n_heads, n_kv_heads, st);
+    if (head_dim == 128) return launch_bwd<128>(name, a, delta_ws, B, L, n_heads, n_kv_heads, st);
+    return launch_bwd<96>(name, a, delta_ws, B, L, n_heads, n_kv_heads, st);
 }

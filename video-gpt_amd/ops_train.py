@@ -52,9 +52,16 @@ def attention_qkv_bwd(qkv, out, dout, lse, delta_ws, dqkv, pm, n_heads, n_kv_hea
     scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
     q, k, v = qkv.data_ptr(), qkv.data_ptr() + hq * 2, qkv.data_ptr() + (hq + hk) * 2
     dq, dk, dv = dqkv.data_ptr(), dqkv.data_ptr() + hq * 2, dqkv.data_ptr() + (hq + hk) * 2
-    call("vgpt_attn_blockmask_bwd", q, k, v, out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta_ws.data_ptr(), dq, dk,
+    # head dim 96 keeps its own entry point (the launches it always had); 64 / 128 go through the per-head-dim one
+    entry = "vgpt_attn_blockmask_bwd" if head_dim == 96 else "vgpt_attn_blockmask_bwd_hd"
+    call(entry, q, k, v, out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta_ws.data_ptr(), dq, dk,
          dv, pm.bits.data_ptr(), pm.summary.data_ptr(), B, L, n_heads, n_kv_heads, head_dim, arr, float(scale), _stream())
     return dqkv
+
+
+def attention_bwd_supported(head_dim: int) -> bool:
+    """True if attention_qkv_bwd has kernels for this head dim (vgpt_attn_bwd_supported)."""
+    return bool(_lib.load().vgpt_attn_bwd_supported(int(head_dim)))
 
 
 def transpose_pad(x2d: torch.Tensor, out: torch.Tensor, rows_padded: int):

@@ -256,6 +256,9 @@ class Stage1Trainer:
         self.gradient_checkpointing = (bool(getattr(model.llm, "gradient_checkpointing", False))
                                        if gradient_checkpointing is None else bool(gradient_checkpointing))
         self.forward_only = forward_only
+        if not forward_only and not T.attention_bwd_supported(self.cfg.head_dim):
+            raise VgptError(f"Stage1Trainer: head_dim {self.cfg.head_dim} cannot train: the attention backward is built for "
+                            f"head dims 64, 96 and 128 (a forward-only trainer needs no backward)")
         self.deterministic = bool(deterministic)
         self.max_grad_norm = max_grad_norm
         self.input_noise = input_noise
