@@ -279,6 +279,35 @@ int vgpt_attn_fwd_plan_fp8(const void* workspace, void* o, const uint32_t* bits,
                            const uint16_t* item_summary, const int32_t* order, int64_t n_items, int64_t B, int64_t L,
                            int n_heads, int n_kv_heads, int head_dim, int64_t o_sb, int64_t o_sh, int64_t o_ss, void* stream);
 
+/* The same three calls for every head dim D of vgpt_attn_fp8_supported() (64, 96, 128).  Same parameters and the same
+ * stride, alignment, null and row_begin rules as the three above, which stay the head_dim 96 entries; refusals are
+ * prefixed with the _hd name and carry the offending value; vgpt_attn_fp8_workspace_bytes_hd returns -1 on a bad shape
+ * or an unsupported head dim.  head_dim 96 runs the kernels of the entries above and produces the same bytes.
+ *
+ * Workspace layout at head dim D (NB = D / 32 blocks of 32 per row; every part starts 256-byte aligned):
+ *   Q8   (B, n_heads, L, D) e4m3: q * scale * log2(e), each block of 32 d divided by its power-of-two scale;
+ *   QS   (B, n_heads, L, 4) E8M0 bytes: byte j < NB is the scale of d block j, bytes >= NB are 127 (D = 128: all four
+ *        are scales; D = 96: byte 3 is 127; D = 64: bytes 2 and 3 are 127);
+ *   KV   (B, n_kv_heads, ceil(L / 64)) records of REC(D) bytes, one per tile of 64 keys (keys >= L: zero payload):
+ *          K8  at 0:                  [key 64][D] e4m3, blocks of 32 along d
+ *          KS  at 64 D:               [key 64][4] E8M0 bytes, as QS
+ *          V8  at 64 D + 256:         [d tile NB][h 2][d 32][32 bytes] e4m3, blocks of the 32 keys of a tile half kb at one d:
+ *                                     key 32 kb + kk is byte 16 kb + (kk & 3) + 4 (kk >> 3) of h = (kk >> 2) & 1
+ *          VS  at 64 D + 256 + 2048 NB: [d tile NB][key half 2][d 32] E8M0 bytes
+ *        REC(D) = 128 D + 256 + 64 NB rounded up to whole KiB (the LDS DMA moves 1-KiB pieces):
+ *        9 KiB at D = 64, 13 KiB at D = 96, 17 KiB at D = 128.
+ * vgpt_attn_fp8_workspace_bytes_hd = align256(B n_heads L D) + align256(B n_heads L 4) + B n_kv_heads ceil(L / 64) REC(D). */
+int vgpt_attn_fp8_supported(int head_dim);
+int64_t vgpt_attn_fp8_workspace_bytes_hd(int64_t B, int64_t L, int n_heads, int n_kv_heads, int head_dim);
+int vgpt_attn_fp8_quantize_hd(const void* q, const void* k, const void* v, void* workspace, int64_t B, int64_t L,
+                              int64_t row_begin, int n_heads, int n_kv_heads, int head_dim, int64_t q_sb, int64_t q_sh,
+                              int64_t q_ss, int64_t k_sb, int64_t k_sh, int64_t k_ss, int64_t v_sb, int64_t v_sh,
+                              int64_t v_ss, float scale, void* stream);
+int vgpt_attn_fwd_plan_fp8_hd(const void* workspace, void* o, const uint32_t* bits, const int32_t* items,
+                              const uint16_t* item_summary, const int32_t* order, int64_t n_items, int64_t B, int64_t L,
+                              int n_heads, int n_kv_heads, int head_dim, int64_t o_sb, int64_t o_sh, int64_t o_ss,
+                              void* stream);
+
 /* ---- MX-fp8 projections (inference option `linear_precision = "fp8"` of the sampler's per-step forward: qkv_proj, o_proj,
  * gate_up_proj, down_proj of every decoder layer).  Number format as the MX-fp8 attention: OCP e4m3 in blocks of 32
  * consecutive k of a row sharing an E8M0 scale 2^e, e the smallest exponent with amax 2^-e <= 448 (clamped to [-127, 127]),
@@ -314,6 +343,13 @@ int vgpt_mx8_quant_weight(const void* W, const void* gain, void* out, int64_t N,
 int vgpt_gemm_mx8(const void* A8, const void* W8, void* C, const void* resid, const float* rstd, const float* cos_t,
                   const float* sin_t, int64_t M, int64_t N, int64_t K, int64_t ldc, int64_t ldr, int epilogue, int n_rot_heads,
                   int head_dim, int act, void* stream);
+/* vgpt_gemm_mx8 whose VGPT_MX8_EPI_ROPE epilogue takes head_dim 64, 96 or 128 (N % head_dim == 0,
+ * n_rot_heads * head_dim <= N, cos / sin (M, head_dim / 2) fp32): one head per wave, so tiles of 128, 192 or 256 columns;
+ * the rotate-half partner of column d of a head is d +- head_dim / 2.  Same parameters as vgpt_gemm_mx8, which stays the
+ * head_dim 96 entry; head_dim 96 runs its kernel, bit for bit; the other three epilogues are vgpt_gemm_mx8 itself. */
+int vgpt_gemm_mx8_hd(const void* A8, const void* W8, void* C, const void* resid, const float* rstd, const float* cos_t,
+                     const float* sin_t, int64_t M, int64_t N, int64_t K, int64_t ldc, int64_t ldr, int epilogue,
+                     int n_rot_heads, int head_dim, int act, void* stream);
 
 /* order (B, ceil(L/128) - q_start/128) int32 <- the 128-row q blocks [q_start/128, ...) of every batch item, the one
  * with the most non-empty 64-key tiles first (stable). */

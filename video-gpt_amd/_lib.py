@@ -70,6 +70,11 @@ SIGNATURES = {
     "vgpt_attn_fp8_workspace_bytes": (_I64, [_I64, _I64, c_int, c_int, c_int]),
     "vgpt_attn_fp8_quantize": (c_int, [_P] * 4 + [_I64, _I64, _I64, c_int, c_int, c_int] + [_I64] * 9 + [c_float, _P]),
     "vgpt_attn_fwd_plan_fp8": (c_int, [_P] * 6 + [_I64, _I64, _I64, c_int, c_int, c_int] + [_I64] * 3 + [_P]),
+    "vgpt_attn_fp8_supported": (c_int, [c_int]),
+    "vgpt_attn_fp8_workspace_bytes_hd": (_I64, [_I64, _I64, c_int, c_int, c_int]),
+    "vgpt_attn_fp8_quantize_hd": (c_int, [_P] * 4 + [_I64, _I64, _I64, c_int, c_int, c_int] + [_I64] * 9 + [c_float, _P]),
+    "vgpt_attn_fwd_plan_fp8_hd": (c_int, [_P] * 6 + [_I64, _I64, _I64, c_int, c_int, c_int] + [_I64] * 3 + [_P]),
+    "vgpt_gemm_mx8_hd": (c_int, [_P] * 7 + [_I64] * 5 + [c_int, c_int, c_int, c_int, _P]),
     "vgpt_mx8_bytes": (_I64, [_I64, _I64]),
     "vgpt_mx8_quant_rows": (c_int, [_P, _I64, _P, _P, _I64, _I64, c_float, _P]),
     "vgpt_mx8_quant_weight": (c_int, [_P, _P, _P, _I64, _I64, _P]),

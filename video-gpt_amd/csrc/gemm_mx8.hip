@@ -22,7 +22,8 @@
 // Kernels:
 //   mx8_quant_kernel   (rows, K) bf16 [x gain (K)] -> record; optionally rstd[m] = rsqrt(mean_k x^2 + eps) of the UNSCALED row
 //                      (the RMSNorm statistic the consumer GEMM's epilogue applies).  8 rows x 32 threads per workgroup.
-//   gemm_mx8_kernel    128-row x (64 WN)-column tiles, four waves as 2 (rows) x 2 (columns), each wave 64 rows x 32 WN columns,
+//   gemm_mx8_kernel    (the RoPE epilogue: one head of 32 WN columns per wave, WN = head_dim / 32 = 2, 3 or 4)
+//                      128-row x (64 WN)-column tiles, four waves as 2 (rows) x 2 (columns), each wave 64 rows x 32 WN columns,
 //                      k tiles of 64 double-buffered in LDS (a simple compiler-scheduled loop).  Every output element is the
 //                      same fixed sequence of MFMAs over k whatever tile or launch computed it: no split-K, no atomics, so a
 //                      row's result does not depend on M or on its position.
@@ -277,23 +278,41 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(GemmArgs a) {
                 }
             }
         } else if constexpr (MODE == MX8_ROPE) {
-            // the wave's three column groups are one head of 96: column d (0..95) and its partner d +- 48 sit in the same lane
-            static_assert(WN == 3, "RoPE tiles hold one head of 96 columns per wave");
-            const int cg0 = (tn * 2 + wn) * 3;
+            // the wave's WN column groups are one head of 32 WN columns: column d and its partner d +- 16 WN sit in the same lane
+            static_assert(WN >= 2 && WN <= 4, "RoPE tiles hold one head of 64, 96 or 128 columns per wave");
+            const int cg0 = (tn * 2 + wn) * WN;
             if (cg0 >= a.NG) continue;
             const bool rot = cg0 * 32 < a.rot_cols;
-            float own[3][16];
+            float own[WN][16];
 #pragma unroll
-            for (int j = 0; j < 3; ++j)
+            for (int j = 0; j < WN; ++j)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) own[j][e] = bf2f(f2bf(acc[i][j][e] * rs));
 #pragma unroll
-            for (int j = 0; j < 3; ++j)
+            for (int j = 0; j < WN; ++j)
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const int d = 32 * j + 8 * g4 + 4 * h;
                     bf16x4 o;
-                    if (rot) {
+                    if constexpr (WN != 3) {
+                        // heads of 64 / 128: the partner d +- 16 WN is column group j +- WN / 2, same g4, same element
+                        if (rot) {
+                            constexpr int HALF = 16 * WN;
+                            const bool upper = j >= WN / 2;
+                            const int pj = upper ? j - WN / 2 : j + WN / 2;
+                            const int dd = upper ? d - HALF : d;
+                            const f32x4 cs = *reinterpret_cast<const f32x4*>(a.cos_t + (int64_t)m * HALF + dd);
+                            const f32x4 sn = *reinterpret_cast<const f32x4*>(a.sin_t + (int64_t)m * HALF + dd);
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const float x = own[j][4 * g4 + u], other = own[pj][4 * g4 + u];
+                                o[u] = f2bf(upper ? x * cs[u] + other * sn[u] : x * cs[u] - other * sn[u]);
+                            }
+                        } else {
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) o[u] = f2bf(own[j][4 * g4 + u]);
+                        }
+                    } else if (rot) {
                         const bool upper = d >= 48;
                         // partner of d: d + 48 = group j + 1, g4 + 2 (or j + 2, g4 - 2); d - 48 the inverse
                         const int pj = upper ? (g4 >= 2 ? j - 1 : j - 2) : (g4 < 2 ? j + 1 : j + 2);
@@ -340,14 +359,14 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(GemmArgs a) {
 }
 
 template <int MODE, int WN>
-int launch_gemm(const GemmArgs& g0, int n_groups_per_tile, hipStream_t stream) {
+int launch_gemm(const GemmArgs& g0, int n_groups_per_tile, hipStream_t stream, const char* name = "vgpt_gemm_mx8") {
     GemmArgs g = g0;
     const int tiles_n = (int)cdiv(g.NG, n_groups_per_tile);
     g.tiles_m = (int)cdiv(g.M, 128);
     const int64_t grid = (int64_t)g.tiles_m * tiles_n;
-    VGPT_REQUIRE(grid < (1ll << 31), VGPT_ERR_UNSUPPORTED, "vgpt_gemm_mx8: problem too large");
+    VGPT_REQUIRE(grid < (1ll << 31), VGPT_ERR_UNSUPPORTED, "%s: problem too large", name);
     hipLaunchKernelGGL((gemm_mx8_kernel<MODE, WN>), dim3((unsigned)grid), dim3(256), 2 * Tile<WN>::STAGE, stream, g);
-    VGPT_CHECK_LAUNCH("vgpt_gemm_mx8");
+    VGPT_CHECK_LAUNCH(name);
     return VGPT_OK;
 }
 
@@ -433,4 +452,45 @@ VGPT_EXPORT int vgpt_gemm_mx8(const void* A8, const void* W8, void* C, const voi
             g.I = (int)(N / 2); g.NG = (int)(N / 64);
             return launch_gemm<MX8_GATED, 4>(g, 4, s);
     }
+}
+
+// vgpt_gemm_mx8 whose RoPE epilogue takes heads of 64, 96 or 128 columns (one head per wave: WN = head_dim / 32); head_dim 96
+// launches the instantiation vgpt_gemm_mx8 launches, the other epilogues are vgpt_gemm_mx8 itself
+VGPT_EXPORT int vgpt_gemm_mx8_hd(const void* A8, const void* W8, void* C, const void* resid, const float* rstd, const float* cos_t,
+                                 const float* sin_t, int64_t M, int64_t N, int64_t K, int64_t ldc, int64_t ldr, int epilogue,
+                                 int n_rot_heads, int head_dim, int act, void* stream) {
+    const char* name = "vgpt_gemm_mx8_hd";
+    VGPT_REQUIRE(epilogue >= VGPT_MX8_EPI_NONE && epilogue <= VGPT_MX8_EPI_GATED, VGPT_ERR_INVALID, "%s: unknown epilogue %d", name,
+                 epilogue);
+    if (epilogue != VGPT_MX8_EPI_ROPE)
+        return vgpt_gemm_mx8(A8, W8, C, resid, rstd, cos_t, sin_t, M, N, K, ldc, ldr, epilogue, n_rot_heads, head_dim, act, stream);
+    VGPT_REQUIRE(A8 && W8 && C, VGPT_ERR_INVALID, "%s: null pointer", name);
+    VGPT_REQUIRE(M > 0 && N > 0 && K > 0 && K % 32 == 0, VGPT_ERR_INVALID,
+                 "%s: M, N > 0 and K a positive multiple of 32 (got %lld, %lld, %lld)", name, (long long)M, (long long)N, (long long)K);
+    VGPT_REQUIRE(N % 32 == 0, VGPT_ERR_UNSUPPORTED, "%s: N must be a multiple of 32 (got %lld)", name, (long long)N);
+    VGPT_REQUIRE(M < (1 << 26) && vgpt_mx8_bytes(M, K) < (1ll << 32) && vgpt_mx8_bytes(N, K) < (1ll << 32), VGPT_ERR_UNSUPPORTED,
+                 "%s: problem too large (M %lld, N %lld, K %lld)", name, (long long)M, (long long)N, (long long)K);
+    VGPT_REQUIRE((((uintptr_t)A8 | (uintptr_t)W8) & 255) == 0 && ((uintptr_t)C & 7) == 0 && ldc % 4 == 0, VGPT_ERR_UNSUPPORTED,
+                 "%s: records 256-byte aligned, C 8-byte aligned with ldc a multiple of 4 (got A8 %p, W8 %p, C %p, ldc %lld)", name, A8,
+                 W8, C, (long long)ldc);
+    VGPT_REQUIRE(ldc >= N, VGPT_ERR_INVALID, "%s: ldc %lld < output columns %lld", name, (long long)ldc, (long long)N);
+    VGPT_REQUIRE(rstd && cos_t && sin_t, VGPT_ERR_INVALID, "%s: null pointer (rstd / cos / sin)", name);
+    VGPT_REQUIRE(head_dim == 64 || head_dim == 96 || head_dim == 128, VGPT_ERR_UNSUPPORTED,
+                 "%s: the RoPE epilogue takes head_dim 64, 96 or 128 (got %d)", name, head_dim);
+    VGPT_REQUIRE(N % head_dim == 0 && n_rot_heads >= 0 && (int64_t)n_rot_heads * head_dim <= N, VGPT_ERR_UNSUPPORTED,
+                 "%s: the RoPE epilogue takes N a multiple of head_dim and n_rot_heads * head_dim <= N (got N %lld, head_dim %d, "
+                 "n_rot_heads %d)", name, (long long)N, head_dim, n_rot_heads);
+    VGPT_REQUIRE((((uintptr_t)cos_t | (uintptr_t)sin_t) & 15) == 0, VGPT_ERR_UNSUPPORTED, "%s: cos / sin 16-byte aligned (got %p, %p)",
+                 name, (const void*)cos_t, (const void*)sin_t);
+    GemmArgs g{};
+    const int64_t KB = cdiv(K, 64);
+    g.a_pay = (const uint8_t*)A8; g.a_sc = g.a_pay + align256(cdiv(M, 32) * KB * 2048);
+    g.w_pay = (const uint8_t*)W8; g.w_sc = g.w_pay + align256(cdiv(N, 32) * KB * 2048);
+    g.C = (bf16*)C; g.resid = nullptr; g.rstd = rstd; g.cos_t = cos_t; g.sin_t = sin_t;
+    g.M = (int)M; g.N = (int)N; g.KB = (int)KB; g.NG = (int)(N / 32); g.I = 0; g.rot_cols = n_rot_heads * head_dim;
+    g.ldc = ldc; g.ldr = ldr; g.act = act;
+    const hipStream_t s = (hipStream_t)stream;
+    if (head_dim == 64) return launch_gemm<MX8_ROPE, 2>(g, 4, s, name);
+    if (head_dim == 128) return launch_gemm<MX8_ROPE, 4>(g, 8, s, name);
+    return launch_gemm<MX8_ROPE, 3>(g, 6, s, name);
 }

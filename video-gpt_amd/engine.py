@@ -177,6 +177,11 @@ class StaticDenoiser:
         self.attn_item_rows = int(os.environ.get("VGPT_ATTN_ITEM_ROWS", "128"))
         self.model = model
         cfg = model.llm.config
+        for opt, on in (("attention_precision", self.attn_fp8), ("linear_precision", self.lin_fp8)):
+            if on and cfg.head_dim not in ops.FP8_HEAD_DIMS:   # refused here, before anything is allocated or launched
+                raise VgptError(f"StaticDenoiser: {opt}='fp8' needs a head dim of {ops.FP8_HEAD_DIMS} (got head_dim "
+                                f"{cfg.head_dim}): the MX-fp8 attention and the qkv + RoPE projection have kernels for those "
+                                "widths only")
         self.cfg = cfg
         dev = input_ids.device
         self.dev = dev
@@ -334,7 +339,7 @@ class StaticDenoiser:
             if self.attn_fp8:
                 # one fp8 workspace per layer (51 MB at cfg-2): prefill() quantises the step-invariant rows once, a step
                 # only the rows from the first one it writes on (the time rows of a hoisted layout sit below S)
-                self.fp8_ws = [ops.attention_fp8_workspace(1, L, nq, nk, hd, dev) for _ in range(cfg.num_hidden_layers)]
+                self.fp8_ws = [ops.attention_fp8_workspace_hd(1, L, nq, nk, hd, dev) for _ in range(cfg.num_hidden_layers)]
                 first = (self.S0 + self.hoist["nf"]) if self.hoist else S
                 self.fp8_from = first // 64 * 64
         else:
@@ -490,7 +495,7 @@ class StaticDenoiser:
             def attention(li):
                 full = self.qkv_full[li].view(1, self.L, -1)
                 if self.attn_fp8:   # the sampler steps read the prefix's K / V from the fp8 workspace of this layer
-                    ops.attention_fp8_quantize(full, self.fp8_ws[li], nq, nk, hd)
+                    ops.attention_fp8_quantize_hd(full, self.fp8_ws[li], nq, nk, hd)
                 ops.attention_qkv_range(full, self.pm, nq, nk, hd, 0, ws.ctx, segments=seg)
             qkv_dst = lambda li: self.qkv_full[li][:S]
         else:
@@ -666,7 +671,7 @@ class StaticDenoiser:
             def attention(li):
                 keep(li)
                 if self.attn_fp8:   # the sampler steps read the cached rows' K / V from the fp8 workspace of this layer
-                    ops.attention_fp8_quantize(self.qkv_full[li].view(1, self.L, -1), self.fp8_ws[li], nq, nk, hd)
+                    ops.attention_fp8_quantize_hd(self.qkv_full[li].view(1, self.L, -1), self.fp8_ws[li], nq, nk, hd)
                 ops.attention_qkv_range(buf.view(1, Lp, W), pm, nq, nk, hd, 0, ws.ctx, segments=seg)
             qkv_dst = lambda li: buf
         else:   # buf collects the rows of every rank for this rank's heads
@@ -838,7 +843,7 @@ class StaticDenoiser:
                 full = self.qkv_full[li].view(1, self.L, -1)
                 if self.attn_fp8:
                     # the prefix rows were quantised once by prefill(); a step re-quantises from the first row it writes
-                    ops.attention_qkv_fp8(full, pm, nq, nk, hd, out=ctx, q_start=S, segments=self.seg_live,
+                    ops.attention_qkv_fp8_hd(full, pm, nq, nk, hd, out=ctx, q_start=S, segments=self.seg_live,
                                           workspace=self.fp8_ws[li], quant_from=self.fp8_from)
                 else:
                     ops.attention_qkv_range(full, pm, nq, nk, hd, S, ctx, segments=self.seg_live, item_rows=rows)
@@ -847,7 +852,7 @@ class StaticDenoiser:
 
             def attention(li):
                 if self.attn_fp8:
-                    ops.attention_qkv_fp8(self.qkv, pm, nq, nk, hd, out=ctx, segments=self.seg_all)
+                    ops.attention_qkv_fp8_hd(self.qkv, pm, nq, nk, hd, out=ctx, segments=self.seg_all)
                 elif self.seg_all is not None:
                     ops.attention_qkv_range(self.qkv, pm, nq, nk, hd, 0, ctx, segments=self.seg_all, item_rows=rows)
                 else:

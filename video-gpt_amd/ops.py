@@ -331,7 +331,8 @@ def linear_mx8(a: Mx8Tensor, w: Mx8Tensor, out: torch.Tensor, epilogue: str = "n
                rstd: Optional[torch.Tensor] = None, cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None,
                n_rot_heads: int = 0, head_dim: int = 96, act: int = ACT_SILU) -> torch.Tensor:
     """MX-fp8 GEMM out = a w^T with an epilogue: "none"; "resid" (+ residual, may be `out`: o_proj / down_proj);
-    "rope" (rows times rstd, RoPE on the first n_rot_heads heads: qkv_proj behind a folded RMSNorm); "gated"
+    "rope" (rows times rstd, RoPE on the first n_rot_heads heads of head_dim 64, 96 or 128: qkv_proj behind a folded
+    RMSNorm); "gated"
     (w = [Wg ; Wu], out (M, N / 2) = act(gate) * up from rows times rstd: gate_up_proj behind a folded RMSNorm)."""
     if epilogue not in _MX8_EPI:
         raise VgptError(f"linear_mx8: unknown epilogue {epilogue!r}")
@@ -360,7 +361,7 @@ def linear_mx8(a: Mx8Tensor, w: Mx8Tensor, out: torch.Tensor, epilogue: str = "n
         _chk(cos, torch.float32, "linear_mx8.cos"); _chk(sin, torch.float32, "linear_mx8.sin")
         if cos.numel() != M * (head_dim // 2) or sin.numel() != cos.numel():
             raise VgptError("linear_mx8: cos / sin table size mismatch")
-    call("vgpt_gemm_mx8", a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(residual), _ptr(rstd), _ptr(cos), _ptr(sin), M, N, K,
+    call("vgpt_gemm_mx8_hd", a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(residual), _ptr(rstd), _ptr(cos), _ptr(sin), M, N, K,
          n_out, N, _MX8_EPI[epilogue], int(n_rot_heads), int(head_dim), int(act), _stream())
     return out
 
@@ -577,6 +578,10 @@ def attention_fp8_workspace(B: int, L: int, n_heads: int, n_kv_heads: int, head_
 def attention_fp8_quantize(qkv: torch.Tensor, ws: torch.Tensor, n_heads: int, n_kv_heads: int, head_dim: int,
                            scale: Optional[float] = None, row_begin: int = 0):
     """Q / K / V of the fused (B, L, .) buffer, rows >= row_begin (a multiple of 64), into the fp8 workspace."""
+    _attention_fp8_quantize("vgpt_attn_fp8_quantize", qkv, ws, n_heads, n_kv_heads, head_dim, scale, row_begin)
+
+
+def _attention_fp8_quantize(entry, qkv, ws, n_heads, n_kv_heads, head_dim, scale, row_begin):
     _chk(qkv, BF16, "attention.qkv")
     B, L, width = qkv.shape
     hq = n_heads * head_dim
@@ -585,7 +590,7 @@ def attention_fp8_quantize(qkv: torch.Tensor, ws: torch.Tensor, n_heads: int, n_
     sb, ss = L * width, width
     if scale is None:
         scale = 1.0 / math.sqrt(head_dim)
-    call("vgpt_attn_fp8_quantize", qkv.data_ptr(), kq, vq, ws.data_ptr(), B, L, int(row_begin), n_heads, n_kv_heads, head_dim,
+    call(entry, qkv.data_ptr(), kq, vq, ws.data_ptr(), B, L, int(row_begin), n_heads, n_kv_heads, head_dim,
          sb, head_dim, ss, sb, head_dim, ss, sb, head_dim, ss, float(scale), _stream())
 
 
@@ -600,6 +605,11 @@ def attention_qkv_fp8(qkv: torch.Tensor, pm: PackedMask, n_heads: int, n_kv_head
     them) against all L keys.  `out` holds rows [q_start, L).  workspace / quant_from: a caller-owned workspace whose rows
     below quant_from (a multiple of 64) already hold their quantised form (the engine's cached prefix); by default a
     shared scratch workspace is filled from row 0.  Inference only; tolerance of fp8 operands."""
+    return _attention_qkv_fp8("", attention_fp8_workspace, qkv, pm, n_heads, n_kv_heads, head_dim, scale, out, q_start, segments,
+                              workspace, quant_from)
+
+
+def _attention_qkv_fp8(sfx, make_ws, qkv, pm, n_heads, n_kv_heads, head_dim, scale, out, q_start, segments, workspace, quant_from):
     _chk(qkv, BF16, "attention.qkv")
     B, L, width = qkv.shape
     if width != (n_heads + 2 * n_kv_heads) * head_dim or B != pm.B or L != pm.L:
@@ -616,14 +626,41 @@ def attention_qkv_fp8(qkv: torch.Tensor, pm: PackedMask, n_heads: int, n_kv_head
         key = (qkv.device, B, L, n_heads, n_kv_heads, head_dim)
         ws = _FP8_WS.get(key)
         if ws is None:
-            ws = _FP8_WS[key] = attention_fp8_workspace(B, L, n_heads, n_kv_heads, head_dim, qkv.device)
-    attention_fp8_quantize(qkv, ws, n_heads, n_kv_heads, head_dim, scale, quant_from)
+            ws = _FP8_WS[key] = make_ws(B, L, n_heads, n_kv_heads, head_dim, qkv.device)
+    _attention_fp8_quantize("vgpt_attn_fp8_quantize" + sfx, qkv, ws, n_heads, n_kv_heads, head_dim, scale, quant_from)
     plan = pm.plan(segments if segments is not None else (tuple((b, q_start, L) for b in range(B))))
     if plan.n_items:
-        call("vgpt_attn_fwd_plan_fp8", ws.data_ptr(), out.data_ptr() - q_start * hq * 2, pm.bits.data_ptr(),
+        call("vgpt_attn_fwd_plan_fp8" + sfx, ws.data_ptr(), out.data_ptr() - q_start * hq * 2, pm.bits.data_ptr(),
              plan.items.data_ptr(), plan.summary.data_ptr(), plan.order.data_ptr(), plan.n_items, B, L, n_heads, n_kv_heads,
              head_dim, (L - q_start) * hq if B > 1 else L * hq, head_dim, hq, _stream())
     return out
+
+
+FP8_HEAD_DIMS = (64, 96, 128)   # vgpt_attn_fp8_supported / the RoPE epilogue of vgpt_gemm_mx8_hd
+
+
+def attention_fp8_workspace_hd(B: int, L: int, n_heads: int, n_kv_heads: int, head_dim: int, device) -> torch.Tensor:
+    """attention_fp8_workspace for every head dim of FP8_HEAD_DIMS (vgpt_attn_fp8_workspace_bytes_hd)."""
+    nbytes = int(_lib.load().vgpt_attn_fp8_workspace_bytes_hd(B, L, n_heads, n_kv_heads, head_dim))
+    if nbytes < 0:
+        raise VgptError(f"attention_fp8: unsupported shape (B {B}, L {L}, n_heads {n_heads}, n_kv_heads {n_kv_heads}, "
+                        f"head_dim {head_dim}: the fp8 kernels are built for {FP8_HEAD_DIMS})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def attention_fp8_quantize_hd(qkv: torch.Tensor, ws: torch.Tensor, n_heads: int, n_kv_heads: int, head_dim: int,
+                              scale: Optional[float] = None, row_begin: int = 0):
+    """attention_fp8_quantize for every head dim of FP8_HEAD_DIMS (vgpt_attn_fp8_quantize_hd)."""
+    _attention_fp8_quantize("vgpt_attn_fp8_quantize_hd", qkv, ws, n_heads, n_kv_heads, head_dim, scale, row_begin)
+
+
+def attention_qkv_fp8_hd(qkv: torch.Tensor, pm: PackedMask, n_heads: int, n_kv_heads: int, head_dim: int,
+                         scale: Optional[float] = None, out: Optional[torch.Tensor] = None, q_start: int = 0, segments=None,
+                         workspace: Optional[torch.Tensor] = None, quant_from: int = 0):
+    """attention_qkv_fp8 for every head dim of FP8_HEAD_DIMS (vgpt_attn_fp8_quantize_hd + vgpt_attn_fwd_plan_fp8_hd); at
+    head dim 96 the same kernels and the same bits."""
+    return _attention_qkv_fp8("_hd", attention_fp8_workspace_hd, qkv, pm, n_heads, n_kv_heads, head_dim, scale, out, q_start,
+                              segments, workspace, quant_from)
 
 
 def sdpa(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, attn_mask=None, dropout_p: float = 0.0,
