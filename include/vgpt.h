@@ -679,6 +679,42 @@ int vgpt_adamw_ema_step(float* master, void* param, const void* grad, int grad_f
  * aligned, a bf16 grad 8-byte aligned (else VGPT_ERR_UNSUPPORTED); a NULL pointer, n < 0 or another mode:
  * VGPT_ERR_INVALID; n == 0: VGPT_OK. */
 int vgpt_grad_accumulate(float* acc, void* grad, int grad_f32, int64_t n, int mode, void* stream);
+/* ---- guarded optimizer step: a non-finite or spiking step is dropped on the device (Stage1Trainer(skip_bad_steps=True),
+ *      DESIGN.md §6f).  Stands in for the overflow check of the reference's optimizer stack: train_x1_stage1_noiseinput.py
+ *      hands AdamW to accelerate's DeepSpeed plugin (:114-125, 393-405; pretrain_stage1_nv.sh:49, stage2_bf16_dp.json), whose
+ *      ZeRO stage-2 optimizer checks the reduced gradients for inf / nan and returns from step() without an update
+ *      (DeepSpeed runtime/zero/stage_1_and_2.py: check_overflow, has_overflow).  The norm threshold has no counterpart there.
+ * vgpt_clip_coef_guarded: vgpt_clip_coef with a verdict.  S, sqrt(S) and the coefficient are formed by the same expressions in
+ *   the same order; verdict (2 int32 words in device memory) = {0, 0}: apply, and coef and *norm_out hold vgpt_clip_coef's
+ *   bits; {1, 1}: skip, sqrt(S) is NaN or Inf (a non-finite or negative S); {1, 2}: skip, skip_norm > 0 and
+ *   sqrt(S) > skip_norm (strictly; skip_norm == 0: no threshold; the caller scales it like max_norm).  A skip writes
+ *   coef = +0.0f; *norm_out (may be NULL) receives sqrt(S) either way.  One wave, the record written by one lane.  A NULL
+ *   sumsq / coef / verdict, n < 1, a negative or NaN max_norm or skip_norm: VGPT_ERR_INVALID, the value named.
+ * vgpt_adamw_step_guarded / vgpt_adamw_ema_step_guarded: vgpt_adamw_step / vgpt_adamw_ema_step behind verdict[0] (device
+ *   memory, the record above).  0: every output has the unguarded entry point's bits (one kernel body).  Non-zero: every
+ *   wave ends behind that one 4-byte load; nothing else is read, nothing is written -- launch overhead instead of 28 / 36
+ *   bytes per parameter.  Same alignment contract (VGPT_ERR_UNSUPPORTED); a NULL pointer, n < 0, step < 1, grad_f32 outside
+ *   {0, 1}, ema_decay outside [0, 1]: VGPT_ERR_INVALID, the value named; n == 0: VGPT_OK.
+ * vgpt_sumsq_keep: vgpt_sumsq that also stores this buffer's own sum: *total += s; *part = s with s the value vgpt_sumsq adds
+ *   (same kernels, same order), so the total keeps its bits and per-bucket gradient norms cost nothing.  n == 0: s = 0.
+ *   A NULL pointer, n < 0, g_f32 outside {0, 1}: VGPT_ERR_INVALID.
+ * vgpt_count_nonfinite (torch.isnan / torch.isinf per tensor, what DeepSpeed's overflow check does not tell): x is a flat
+ *   bf16 (x_f32 = 0) or fp32 (1) buffer of n elements, 16-byte aligned; offsets T + 1 ascending int64 element offsets in
+ *   device memory (clamped to [0, n]); counts[2 t] = number of NaN, counts[2 t + 1] = number of +-Inf in
+ *   [offsets[t], offsets[t + 1]), int32, cleared by the call.  Segments may be empty and start at any element.  Read off
+ *   the bit patterns, integer sums: deterministic.  A diagnostic for after a skip, one pass over the buffer.  A NULL x /
+ *   counts / offsets, n < 0, T outside [0, 65535], x_f32 outside {0, 1}: VGPT_ERR_INVALID; T == 0: VGPT_OK. */
+int vgpt_clip_coef_guarded(const float* sumsq, int n, float* coef, float* norm_out, float max_norm, float extra_scale,
+                           float skip_norm, int32_t* verdict, void* stream);
+int vgpt_adamw_step_guarded(float* master, void* param, const void* grad, int grad_f32, float* m, float* v, int64_t n,
+                            float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                            const float* grad_scale, const int32_t* verdict, void* stream);
+int vgpt_adamw_ema_step_guarded(float* master, void* param, const void* grad, int grad_f32, float* m, float* v, int64_t n,
+                                float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                const float* grad_scale, float* ema, float ema_decay, const int32_t* verdict, void* stream);
+int vgpt_sumsq_keep(const void* g, int g_f32, float* total, float* part, int64_t n, float* partial_ws /* >= 1024 floats */,
+                    void* stream);
+int vgpt_count_nonfinite(const void* x, int x_f32, int64_t n, const int64_t* offsets, int T, int32_t* counts, void* stream);
 
 /* ---- LoRA adapters (LVM/train/train_x1_stage1_noiseinput.py:204-223, peft LoraConfig on qkv_proj / o_proj; the merge of
  *      LVM/pipeline.py:97-101) ------------------------------------------------------------------------------------------

@@ -145,6 +145,13 @@ SIGNATURES = {
     "vgpt_adamw_ema_step": (c_int, [_P, _P, _P, c_int, _P, _P, _I64, c_float, c_float, c_float, c_float, c_float, c_int,
                                     _P, _P, c_float, _P]),
     "vgpt_grad_accumulate": (c_int, [_P, _P, c_int, _I64, c_int, _P]),
+    "vgpt_clip_coef_guarded": (c_int, [_P, c_int, _P, _P, c_float, c_float, c_float, _P, _P]),
+    "vgpt_adamw_step_guarded": (c_int, [_P, _P, _P, c_int, _P, _P, _I64, c_float, c_float, c_float, c_float, c_float, c_int,
+                                        _P, _P, _P]),
+    "vgpt_adamw_ema_step_guarded": (c_int, [_P, _P, _P, c_int, _P, _P, _I64, c_float, c_float, c_float, c_float, c_float,
+                                            c_int, _P, _P, c_float, _P, _P]),
+    "vgpt_sumsq_keep": (c_int, [_P, c_int, _P, _P, _I64, _P, _P]),
+    "vgpt_count_nonfinite": (c_int, [_P, c_int, _I64, _P, c_int, _P, _P]),
     "vgpt_lora_down": (c_int, [_P, _P, _P, _I64, _I64, c_int, _I64, c_int, c_float, _P]),
     "vgpt_lora_up_add": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, c_int, _I64, c_int, c_int, c_int, c_int, c_float, _P]),
     "vgpt_lora_grad_workspace_bytes": (_I64, [_I64, _I64, c_int]),

@@ -790,13 +790,20 @@ __global__ __launch_bounds__(64) void sumsq_final_kernel(const float* __restrict
 // Four elements per thread: 16-byte accesses on the three fp32 streams (28 B/param of traffic, HBM-bound).
 // EMA (vgpt_adamw_ema_step): a fourth fp32 stream in the same pass, ema = fmaf(d, ema, (1 - d) * p_new) on the fp32 master
 // value just computed (36 B/param); a template parameter, so the plain instantiation carries none of it.
-template <typename TG, bool EMA>
+// Guarded twin (vgpt_adamw_step_guarded / vgpt_adamw_ema_step_guarded): the trailing pack V is empty (the kernel
+// vgpt_adamw_step always launched, argument for argument) or one `const int32_t*`, the verdict of vgpt_clip_coef_guarded:
+// verdict[0] != 0 ends every wave behind that one 4-byte load, before the gradient scale or any stream is touched: nothing
+// else is read, nothing is written.  One body, so an applied guarded step has the unguarded step's bits.
+template <typename TG, bool EMA, typename... V>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, bf16* __restrict__ param,
                                                     const TG* __restrict__ grad, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, float lr, float b1, float b2,
                                                     float eps, float wd, float bc1, float bc2,
                                                     const float* __restrict__ grad_scale_ptr, float* __restrict__ ema,
-                                                    float ema_d, float ema_omd) {
+                                                    float ema_d, float ema_omd, V... verdict) {
+    if constexpr (sizeof...(V) != 0) {
+        if ([](const int32_t* p) { return *p; }(verdict...) != 0) return;
+    }
     const float gs = grad_scale_ptr ? *grad_scale_ptr : 1.0f;
     // torch.optim.AdamW: p -= lr (m/bc1) / (sqrt(v/bc2) + eps).  The two bias corrections are folded into constants
     // and the one remaining division is v_rcp_f32 (1 ulp) on a term that is ~lr relative to p.
@@ -901,6 +908,83 @@ __global__ __launch_bounds__(64) void clip_coef_kernel(const float* __restrict__
     if (norm_out) *norm_out = nrm;
     float c = max_norm > 0.f ? max_norm / (nrm + 1e-6f) : 1.0f;
     *coef = fminf(c, 1.0f) * extra;
+}
+// vgpt_clip_coef_guarded: clip_coef_kernel's sum, norm and coefficient by the same expressions in the same order, and a
+// verdict in front of the coefficient: {1, 1} when sqrt(S) is not finite (S is NaN, +-Inf, or negative), {1, 2} when
+// skip_norm > 0 and sqrt(S) > skip_norm, else {0, 0}.  Finiteness is read off the exponent bits.  A skip writes coef = +0.
+// One lane writes the record with plain stores; the copy to the host and the guarded AdamW launches are stream-ordered
+// behind this kernel.
+__global__ __launch_bounds__(64) void clip_coef_guarded_kernel(const float* __restrict__ sumsq, int n, float* coef,
+                                                               float* norm_out, float max_norm, float extra,
+                                                               float skip_norm, int32_t* verdict) {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += 64) s += sumsq[i];
+    s = wave_sum(s);
+    if (threadIdx.x != 0) return;
+    const float nrm = sqrtf(s);
+    if (norm_out) *norm_out = nrm;
+    const bool finite = (__float_as_uint(nrm) & 0x7f800000u) != 0x7f800000u;
+    const int reason = !finite ? 1 : (skip_norm > 0.f && nrm > skip_norm) ? 2 : 0;
+    verdict[0] = reason != 0;
+    verdict[1] = reason;
+    if (reason) { *coef = 0.0f; return; }
+    float c = max_norm > 0.f ? max_norm / (nrm + 1e-6f) : 1.0f;
+    *coef = fminf(c, 1.0f) * extra;
+}
+
+// sumsq_final_kernel that also keeps the bucket's own sum: the same adds in the same order, then *out += s; *part = s
+__global__ __launch_bounds__(64) void sumsq_final_keep_kernel(const float* __restrict__ partial, int n_partial,
+                                                              float* __restrict__ out, float* __restrict__ part) {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n_partial; i += 64) s += partial[i];
+    s = wave_sum(s);
+    if (threadIdx.x == 0) { *out += s; *part = s; }
+}
+
+// vgpt_count_nonfinite: NaN and +-Inf per segment [off[t], off[t+1]) of a flat buffer of n elements, read off the bit
+// patterns (exponent all ones; mantissa non-zero: NaN, zero: Inf).  blockIdx.y is the segment, the blocks of a row stride
+// over it: the elements in front of the first 16-byte boundary and behind the last one singly (the first threads of block
+// 0), the rest as 16-byte vectors.  Integer sums and integer atomics: the counts do not depend on the order.
+// U: uint16_t (bf16) or uint32_t (fp32).
+template <typename U>
+__global__ __launch_bounds__(256) void count_nonfinite_kernel(const U* __restrict__ x, int64_t n,
+                                                              const int64_t* __restrict__ off,
+                                                              int32_t* __restrict__ counts) {
+    constexpr int V = 16 / sizeof(U);
+    constexpr U EXP = sizeof(U) == 2 ? (U)0x7f80u : (U)0x7f800000u, ABS = sizeof(U) == 2 ? (U)0x7fffu : (U)0x7fffffffu;
+    using vec = U __attribute__((ext_vector_type(V)));
+    const int t = blockIdx.y;
+    // clamped to the buffer: whatever the table holds, nothing outside [0, n) is read
+    const int64_t a = off[t] < 0 ? 0 : off[t], b = off[t + 1] > n ? n : off[t + 1];
+    if (b <= a) return;
+    int n_nan = 0, n_inf = 0;
+    auto look = [&](U u) {
+        const U m = u & ABS;
+        n_nan += m > EXP;
+        n_inf += m == EXP;
+    };
+    // [a, a1): head, [a1, b1): whole 16-byte vectors of the buffer (x itself is 16-byte aligned), [b1, b): tail
+    const int64_t a1 = (a + V - 1) / V * V < b ? (a + V - 1) / V * V : b, b1 = a1 + (b - a1) / V * V;
+    for (int64_t i = a1 / V + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < b1 / V; i += (int64_t)gridDim.x * blockDim.x) {
+        const vec u = reinterpret_cast<const vec*>(x)[i];
+#pragma unroll
+        for (int j = 0; j < V; ++j) look(u[j]);
+    }
+    if (blockIdx.x == 0) {
+        for (int64_t i = a + threadIdx.x; i < a1; i += blockDim.x) look(x[i]);
+        for (int64_t i = b1 + threadIdx.x; i < b; i += blockDim.x) look(x[i]);
+    }
+    __shared__ int red[2][4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { n_nan += __shfl_xor(n_nan, o, 64); n_inf += __shfl_xor(n_inf, o, 64); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = n_nan; red[1][threadIdx.x >> 6] = n_inf; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        n_nan = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        n_inf = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        if (n_nan) atomicAdd(&counts[2 * t], n_nan);
+        if (n_inf) atomicAdd(&counts[2 * t + 1], n_inf);
+    }
 }
 
 template <int MAXN>
@@ -1287,10 +1371,68 @@ VGPT_EXPORT int vgpt_clip_coef(const float* sumsq, int n, float* coef, float* no
     LAUNCH_OK("vgpt_clip_coef");
 }
 
-// shared by vgpt_adamw_step (ema == NULL) and vgpt_adamw_ema_step
+VGPT_EXPORT int vgpt_sumsq_keep(const void* g, int g_f32, float* total, float* part, int64_t n, float* partial_ws,
+                                void* stream) {
+    VGPT_REQUIRE(g && total && part && partial_ws, VGPT_ERR_INVALID,
+                 "vgpt_sumsq_keep: null pointer (g %p, total %p, part %p, partial_ws %p)", g, (void*)total, (void*)part,
+                 (void*)partial_ws);
+    VGPT_REQUIRE(n >= 0, VGPT_ERR_INVALID, "vgpt_sumsq_keep: negative length n = %lld", (long long)n);
+    VGPT_REQUIRE(g_f32 == 0 || g_f32 == 1, VGPT_ERR_INVALID, "vgpt_sumsq_keep: g_f32 = %d, expected 0 (bf16) or 1 (fp32)", g_f32);
+    // n == 0: an empty sum, one wave over zero partials (total += 0, part = 0); grid as vgpt_sumsq's
+    int grid = (int)std::min<int64_t>(cdiv(n, 256 * 8), 1024);
+    if (grid > 0) {
+        if (g_f32)
+            hipLaunchKernelGGL(sumsq_partial_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)g,
+                               partial_ws, n);
+        else
+            hipLaunchKernelGGL(sumsq_partial_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)g,
+                               partial_ws, n);
+    }
+    hipLaunchKernelGGL(sumsq_final_keep_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial_ws, grid, total, part);
+    LAUNCH_OK("vgpt_sumsq_keep");
+}
+
+VGPT_EXPORT int vgpt_clip_coef_guarded(const float* sumsq, int n, float* coef, float* norm_out, float max_norm,
+                                       float extra_scale, float skip_norm, int32_t* verdict, void* stream) {
+    VGPT_REQUIRE(sumsq && coef && verdict, VGPT_ERR_INVALID, "vgpt_clip_coef_guarded: null pointer (sumsq %p, coef %p, verdict %p)",
+                 (const void*)sumsq, (void*)coef, (void*)verdict);
+    VGPT_REQUIRE(n >= 1, VGPT_ERR_INVALID, "vgpt_clip_coef_guarded: n = %d partial sums, must be >= 1", n);
+    VGPT_REQUIRE(max_norm >= 0.f, VGPT_ERR_INVALID, "vgpt_clip_coef_guarded: max_norm = %g, must be >= 0 (0: no clipping)",
+                 (double)max_norm);      // a NaN fails the comparison too
+    VGPT_REQUIRE(skip_norm >= 0.f, VGPT_ERR_INVALID, "vgpt_clip_coef_guarded: skip_norm = %g, must be >= 0 (0: no threshold)",
+                 (double)skip_norm);
+    hipLaunchKernelGGL(clip_coef_guarded_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sumsq, n, coef, norm_out, max_norm,
+                       extra_scale, skip_norm, verdict);
+    LAUNCH_OK("vgpt_clip_coef_guarded");
+}
+
+VGPT_EXPORT int vgpt_count_nonfinite(const void* x, int x_f32, int64_t n, const int64_t* offsets, int T, int32_t* counts,
+                                     void* stream) {
+    VGPT_REQUIRE(x && counts, VGPT_ERR_INVALID, "vgpt_count_nonfinite: null pointer (x %p, counts %p)", x, (void*)counts);
+    VGPT_REQUIRE(offsets, VGPT_ERR_INVALID, "vgpt_count_nonfinite: null offsets table");
+    VGPT_REQUIRE(T >= 0 && T <= 65535, VGPT_ERR_INVALID, "vgpt_count_nonfinite: T = %d segments, expected 0 <= T <= 65535", T);
+    VGPT_REQUIRE(x_f32 == 0 || x_f32 == 1, VGPT_ERR_INVALID, "vgpt_count_nonfinite: x_f32 = %d, expected 0 (bf16) or 1 (fp32)", x_f32);
+    VGPT_REQUIRE(n >= 0, VGPT_ERR_INVALID, "vgpt_count_nonfinite: negative length n = %lld", (long long)n);
+    VGPT_REQUIRE(((uintptr_t)x & 15) == 0, VGPT_ERR_UNSUPPORTED, "vgpt_count_nonfinite: x = %p must be 16-byte aligned", x);
+    if (T == 0) return VGPT_OK;
+    VGPT_REQUIRE(hipMemsetAsync(counts, 0, (size_t)T * 2 * sizeof(int32_t), (hipStream_t)stream) == hipSuccess, VGPT_ERR_HIP,
+                 "vgpt_count_nonfinite: clearing the counts failed");
+    // the blocks of a row share one segment; sized for the longest there can be, the whole buffer
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256 * 32), 256)), (unsigned)T);
+    if (x_f32)
+        hipLaunchKernelGGL(count_nonfinite_kernel<uint32_t>, grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t*)x,
+                           n, offsets, counts);
+    else
+        hipLaunchKernelGGL(count_nonfinite_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
+                           n, offsets, counts);
+    LAUNCH_OK("vgpt_count_nonfinite");
+}
+
+// shared by vgpt_adamw_step (ema == NULL), vgpt_adamw_ema_step and their guarded twins (verdict != NULL)
 static int adamw_launch(const char* name, float* master, void* param, const void* grad, int grad_f32, float* m, float* v,
                         int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                        const float* grad_scale, float* ema, float ema_decay, void* stream) {
+                        const float* grad_scale, float* ema, float ema_decay, void* stream,
+                        const int32_t* verdict = nullptr) {
     // in double, as torch.optim.AdamW does: 1 - beta2^step cancels at small steps (1 - powf(0.999f, 2) in fp32 is 6.7e-6
     // off, relative), and that error went straight into every update of the first steps
     const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step)),
@@ -1305,9 +1447,18 @@ static int adamw_launch(const char* name, float* master, void* param, const void
     hipLaunchKernelGGL((adamw_kernel<TG, EMA>), dim3(grid), dim3(256), 0, (hipStream_t)stream, master, (bf16*)param,      \
                        (const TG*)grad, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, ema, ema_decay, \
                        omd)
+#define VGPT_ADAMW_GUARDED_LAUNCH(TG, EMA)                                                                                \
+    hipLaunchKernelGGL((adamw_kernel<TG, EMA, const int32_t*>), dim3(grid), dim3(256), 0, (hipStream_t)stream, master,            \
+                       (bf16*)param, (const TG*)grad, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale,   \
+                       ema, ema_decay, omd, verdict)
+    if (verdict) {      // the same grid: a skipped launch is that many waves that end behind one load
+        if (ema) { if (grad_f32) VGPT_ADAMW_GUARDED_LAUNCH(float, true); else VGPT_ADAMW_GUARDED_LAUNCH(bf16, true); }
+        else     { if (grad_f32) VGPT_ADAMW_GUARDED_LAUNCH(float, false); else VGPT_ADAMW_GUARDED_LAUNCH(bf16, false); }
+    } else
     if (ema) { if (grad_f32) VGPT_ADAMW_LAUNCH(float, true); else VGPT_ADAMW_LAUNCH(bf16, true); }
     else     { if (grad_f32) VGPT_ADAMW_LAUNCH(float, false); else VGPT_ADAMW_LAUNCH(bf16, false); }
 #undef VGPT_ADAMW_LAUNCH
+#undef VGPT_ADAMW_GUARDED_LAUNCH
     VGPT_CHECK_LAUNCH(name);
     return VGPT_OK;
 }
@@ -1331,6 +1482,43 @@ VGPT_EXPORT int vgpt_adamw_ema_step(float* master, void* param, const void* grad
     if (n == 0) return VGPT_OK;
     return adamw_launch("vgpt_adamw_ema_step", master, param, grad, grad_f32, m, v, n, lr, beta1, beta2, eps, weight_decay,
                         step, grad_scale, ema, ema_decay, stream);
+}
+
+// what both guarded entry points refuse, each value named
+static int adamw_guarded_check(const char* name, const void* master, const void* param, const void* grad, int grad_f32,
+                               const void* m, const void* v, int64_t n, int step, const int32_t* verdict) {
+    VGPT_REQUIRE(master && param && grad && m && v, VGPT_ERR_INVALID, "%s: null pointer (master %p, param %p, grad %p, m %p, v %p)",
+                 name, master, param, grad, m, v);
+    VGPT_REQUIRE(verdict, VGPT_ERR_INVALID, "%s: null verdict", name);
+    VGPT_REQUIRE(((uintptr_t)verdict & 3) == 0, VGPT_ERR_UNSUPPORTED, "%s: verdict = %p must be 4-byte aligned", name,
+                 (const void*)verdict);
+    VGPT_REQUIRE(grad_f32 == 0 || grad_f32 == 1, VGPT_ERR_INVALID, "%s: grad_f32 = %d, expected 0 (bf16) or 1 (fp32)", name, grad_f32);
+    VGPT_REQUIRE(n >= 0, VGPT_ERR_INVALID, "%s: negative length n = %lld", name, (long long)n);
+    VGPT_REQUIRE(step >= 1, VGPT_ERR_INVALID, "%s: step = %d, must be >= 1", name, step);
+    return VGPT_OK;
+}
+
+VGPT_EXPORT int vgpt_adamw_step_guarded(float* master, void* param, const void* grad, int grad_f32, float* m, float* v,
+                                        int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                        int step, const float* grad_scale, const int32_t* verdict, void* stream) {
+    const int rc = adamw_guarded_check("vgpt_adamw_step_guarded", master, param, grad, grad_f32, m, v, n, step, verdict);
+    if (rc != VGPT_OK || n == 0) return rc;
+    return adamw_launch("vgpt_adamw_step_guarded", master, param, grad, grad_f32, m, v, n, lr, beta1, beta2, eps, weight_decay,
+                        step, grad_scale, nullptr, 0.f, stream, verdict);
+}
+
+VGPT_EXPORT int vgpt_adamw_ema_step_guarded(float* master, void* param, const void* grad, int grad_f32, float* m, float* v,
+                                            int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                            int step, const float* grad_scale, float* ema, float ema_decay,
+                                            const int32_t* verdict, void* stream) {
+    const int rc = adamw_guarded_check("vgpt_adamw_ema_step_guarded", master, param, grad, grad_f32, m, v, n, step, verdict);
+    if (rc != VGPT_OK) return rc;
+    VGPT_REQUIRE(ema, VGPT_ERR_INVALID, "vgpt_adamw_ema_step_guarded: null ema");
+    VGPT_REQUIRE(ema_decay >= 0.f && ema_decay <= 1.f, VGPT_ERR_INVALID,
+                 "vgpt_adamw_ema_step_guarded: ema_decay = %g, expected 0 <= decay <= 1", (double)ema_decay);
+    if (n == 0) return VGPT_OK;
+    return adamw_launch("vgpt_adamw_ema_step_guarded", master, param, grad, grad_f32, m, v, n, lr, beta1, beta2, eps,
+                        weight_decay, step, grad_scale, ema, ema_decay, stream, verdict);
 }
 
 VGPT_EXPORT int vgpt_grad_accumulate(float* acc, void* grad, int grad_f32, int64_t n, int mode, void* stream) {

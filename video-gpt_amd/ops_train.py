@@ -271,6 +271,64 @@ def grad_accumulate(acc, grad, mode):
     call("vgpt_grad_accumulate", acc.data_ptr(), grad.data_ptr(), _f32flag(grad), acc.numel(), int(mode), _stream())
 
 
+I32 = torch.int32
+
+
+def _verdict_ptr(verdict, who):
+    if not verdict.is_cuda or verdict.dtype != I32 or not verdict.is_contiguous() or verdict.numel() < 2:
+        raise VgptError(f"{who}: verdict must be a contiguous int32 GPU tensor of at least 2 words")
+    return verdict.data_ptr()
+
+
+def sumsq_keep(g, total, part):
+    """sumsq that also stores g's own sum in `part` (1 fp32): total += s, part = s (vgpt_sumsq_keep)."""
+    _chk(part, F32, "sumsq_keep.part")
+    ws = _partials.get(g.device)
+    if ws is None:
+        ws = _partials[g.device] = torch.empty(1024, dtype=F32, device=g.device)
+    call("vgpt_sumsq_keep", g.data_ptr(), _f32flag(g), total.data_ptr(), part.data_ptr(), g.numel(), ws.data_ptr(), _stream())
+
+
+def clip_coef_guarded(sumsq_t, coef, norm_out, max_norm, extra_scale, skip_norm, verdict):
+    """clip_coef that also writes verdict = {skip?, reason} (int32; reason 1: the norm is not finite, 2: it exceeds
+    skip_norm > 0) and coef = +0 on a skip (vgpt_clip_coef_guarded).  skip_norm 0: no threshold."""
+    if not sumsq_t.is_cuda or sumsq_t.dtype != F32 or not sumsq_t.is_contiguous():
+        raise VgptError("clip_coef_guarded: sumsq must be a contiguous fp32 GPU tensor")
+    call("vgpt_clip_coef_guarded", sumsq_t.data_ptr(), sumsq_t.numel(), coef.data_ptr(), _ptr(norm_out), float(max_norm),
+         float(extra_scale), float(skip_norm), _verdict_ptr(verdict, "clip_coef_guarded"), _stream())
+
+
+def adamw_step_guarded(master, param, grad, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale, verdict):
+    """adamw_step that does nothing at all when verdict[0] != 0 on the device (vgpt_adamw_step_guarded)."""
+    call("vgpt_adamw_step_guarded", master.data_ptr(), param.data_ptr(), grad.data_ptr(), _f32flag(grad), m.data_ptr(),
+         v.data_ptr(), master.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+         _ptr(grad_scale), _verdict_ptr(verdict, "adamw_step_guarded"), _stream())
+
+
+def adamw_ema_step_guarded(master, param, grad, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale, ema, ema_decay,
+                           verdict):
+    """adamw_ema_step that does nothing at all when verdict[0] != 0 on the device (vgpt_adamw_ema_step_guarded)."""
+    _chk(ema, F32, "adamw_ema_step_guarded.ema")
+    if ema.numel() != master.numel():
+        raise VgptError("adamw_ema_step_guarded: ema and master differ in length")
+    call("vgpt_adamw_ema_step_guarded", master.data_ptr(), param.data_ptr(), grad.data_ptr(), _f32flag(grad), m.data_ptr(),
+         v.data_ptr(), master.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+         _ptr(grad_scale), ema.data_ptr(), float(ema_decay), _verdict_ptr(verdict, "adamw_ema_step_guarded"), _stream())
+
+
+def count_nonfinite(x, offsets):
+    """(T, 2) int32 GPU tensor: per segment [offsets[t], offsets[t + 1]) of the flat bf16 / fp32 buffer x the number of NaN
+    and of +-Inf (vgpt_count_nonfinite).  offsets: T + 1 ascending int64 element offsets, on the GPU."""
+    if not x.is_cuda or not x.is_contiguous():
+        raise VgptError("count_nonfinite: x must be a contiguous GPU tensor")
+    if not offsets.is_cuda or offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.numel() < 1:
+        raise VgptError("count_nonfinite: offsets must be a contiguous int64 GPU tensor of T + 1 entries")
+    T_ = offsets.numel() - 1
+    counts = torch.empty(T_, 2, dtype=I32, device=x.device)
+    call("vgpt_count_nonfinite", x.data_ptr(), _f32flag(x), x.numel(), offsets.data_ptr(), T_, counts.data_ptr(), _stream())
+    return counts
+
+
 def linear_dx(dy2d, weight, scratch=None, dres=None, out=None):
     """dX (M, K) = dY (M, N) @ W (N, K) (+ dres): the weight is read as the transposed operand of the GEMM
     (include/vgpt.h, vgpt_gemm_bf16_tr); `scratch` is unused (kept for callers of the transposing version)."""

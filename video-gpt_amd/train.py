@@ -28,7 +28,10 @@ optimizer to DeepSpeed's bf16 AdamW (fp32 master weights).  Here:
     LVM/transform/sdpa_transform.py:94-159, LVM/utils.py:148-174) shares the rows of ONE packed clip between the P ranks:
     the row-local work of forward and backward runs on this rank's share, attention and its backward on this rank's heads
     over all rows, with two exchanges per layer each way; every saved activation is 1/P of the unsharded step's and the
-    gradient buckets hold partial sums over the share that the data-parallel exchange adds up.
+    gradient buckets hold partial sums over the share that the data-parallel exchange adds up (DESIGN.md §6c);
+  * skip_bad_steps=True drops a step whose gradient norm is not finite (or exceeds skip_grad_norm_above) on the device: the
+    clip kernel writes a verdict, the AdamW launches read it and do nothing, the host learns of it one step later
+    (what the reference gets from DeepSpeed's overflow check).
 """
 from __future__ import annotations
 
@@ -65,6 +68,23 @@ def lora_key(layer: int, module: str, ab: str) -> str:
 # dp_sharding="optimizer": every flat bucket is padded to a multiple of world * SHARD_GRANULE elements, so each rank's
 # shard starts 512 (bf16) / 1024 (fp32) bytes apart: vgpt_adamw_step's alignment check and vgpt_sumsq's 16-byte loads
 SHARD_GRANULE = 256
+SKIP_REASONS = {0: None, 1: "nonfinite", 2: "grad_norm"}       # verdict[1] of vgpt_clip_coef_guarded
+
+
+def check_guard_arguments(skip_bad_steps, skip_grad_norm_above, forward_only: bool = False):
+    """Stage1Trainer's refusals of skip_bad_steps / skip_grad_norm_above, on the arguments alone (no model, no device);
+    returns the threshold as a float, or None."""
+    if skip_grad_norm_above is not None:
+        thr = skip_grad_norm_above
+        if isinstance(thr, bool) or not isinstance(thr, (int, float)) or not (0.0 < float(thr) < math.inf):
+            raise VgptError(f"skip_grad_norm_above {thr!r}: expected a positive finite norm (or None)")
+        if not skip_bad_steps:
+            raise VgptError(f"skip_grad_norm_above {thr!r} without skip_bad_steps=True: the threshold is part of the guarded "
+                            "step")
+    if skip_bad_steps and forward_only:
+        raise VgptError("skip_bad_steps with forward_only: there is no optimizer step to skip, the guard of a forward-only "
+                        "trainer is not built")
+    return None if skip_grad_norm_above is None else float(skip_grad_norm_above)
 
 
 def shard_partition(n: int, world: int):
@@ -164,7 +184,7 @@ class Stage1Trainer:
                  gradient_accumulation_steps: int = 1, use_ema: bool = False, ema_decay: float = 0.9999,
                  lr_num_training_steps: Optional[int] = None, lr_num_cycles: Optional[float] = None,
                  lr_power: float = 1.0, sequence_parallel: bool = False, sp_group=None, check_sp_inputs: bool = True,
-                 deterministic: bool = False):
+                 deterministic: bool = False, skip_bad_steps: bool = False, skip_grad_norm_above: Optional[float] = None):
         """lr_scheduler / lr_warmup_steps / lr_num_training_steps / lr_num_cycles / lr_power: diffusers' get_scheduler
         (train_x1_stage1_noiseinput.py:279-283, 513-521; the scripts use constant_with_warmup), one of LR_SCHEDULERS: the
         k-th optimizer step (k = 0, 1, ...) runs at lr * lr_factor(name, k * lr_scheduler_steps_per_optimizer_step, ...);
@@ -218,7 +238,22 @@ class Stage1Trainer:
         deterministic: the three reductions of the step that add with fp32 atomics (RMSNorm gain gradients, the final
         layer's dshift / dscale, the embedding-table gradient) run their fixed-order twins (vgpt_*_det), which makes the
         step a pure function of its inputs: same inputs, build, world size and collective library give the same bits
-        (DESIGN.md §6d).  Composes with every other option; nothing to do in a forward-only trainer."""
+        (DESIGN.md §6d).  Composes with every other option; nothing to do in a forward-only trainer.
+        skip_bad_steps / skip_grad_norm_above (the overflow check of the reference's DeepSpeed optimizer,
+        which this trainer's own kernels replaced): an optimizer step whose global gradient norm is NaN or Inf -- or, with
+        a threshold, whose norm of the MEAN gradient over ranks and micro-batches (the quantity max_grad_norm clips)
+        exceeds skip_grad_norm_above -- is dropped on the device and leaves no trace: masters, moments, EMA, parameters,
+        step_count, the AdamW bias-correction step and the LR schedule position stay where they were (all three count
+        APPLIED steps).  The verdict is taken by the clip kernel from the one sum of squares every rank already agrees on
+        bit for bit (no new collective, no extra pass over the gradients) and read by the AdamW launches on the device;
+        the host copies it to pinned memory behind an event and looks at it when it issues the next optimizer stage, or
+        when step_count, current_lr(), skipped_steps, last_step_skipped, last_skip_reason or save_checkpoint() is
+        asked: no device-wide synchronisation inside step().  On good data the guarded run is bit-identical to the
+        unguarded one.  bucket_grad_norms() and nonfinite_report() say where a bad step came from.  Refused on a
+        forward-only trainer; the threshold is positive, finite and needs skip_bad_steps=True."""
+        self.skip_grad_norm_above = check_guard_arguments(skip_bad_steps, skip_grad_norm_above, forward_only)   # before anything is touched
+        self.skip_bad_steps = bool(skip_bad_steps)
+        self._skipped, self._last_skipped, self._last_reason = 0, False, None
         model._check_ready()
         if hasattr(model, "release_engines"):
             model.release_engines()          # a sampler engine cached on the model holds GBs the trainer's buffers want
@@ -454,6 +489,7 @@ class Stage1Trainer:
             self.lora_master = host.to(self.dev)
             self.lora_m, self.lora_v = torch.zeros_like(self.lora_master), torch.zeros_like(self.lora_master)
             self.lora_bucket = torch.zeros(o, dtype=F32, device=self.dev)
+            self._lora_sizes = [shape[0] * shape[1] for *_, shape in slots]      # padded slot lengths, the bucket's layout
         self._lora_w, self._lora_g = {}, {}      # (layer, module) -> padded (A, B) views of the working copy / the gradient
         for i, mod, ab, off, shape in slots:
             name = lora_key(i, mod, ab)
@@ -516,6 +552,95 @@ class Stage1Trainer:
             T.adamw_ema_step(master, param, grad, m_, v_, lr, b1, b2, self.eps, self.wd, self.step_count, self.coef, ema,
                              self.ema_decay)
 
+    def _adamw_guarded(self, master, param, grad, m_, v_, ema, lr, b1, b2):
+        """_adamw behind the verdict of this step's clip kernel.  The step number is the host's count as if this step
+        applies (_step_count, read without resolving the verdict in flight): a skipped launch never looks at it."""
+        if ema is None:
+            T.adamw_step_guarded(master, param, grad, m_, v_, lr, b1, b2, self.eps, self.wd, self._step_count, self.coef,
+                                 self._verdict)
+        else:
+            T.adamw_ema_step_guarded(master, param, grad, m_, v_, lr, b1, b2, self.eps, self.wd, self._step_count, self.coef,
+                                     ema, self.ema_decay, self._verdict)
+
+    # ---- guarded step: the verdict in flight and what the host knows of it (DESIGN.md §6f) ---------------------------
+    _pending = None      # event behind the copy of the last verdict to pinned memory; None: nothing to resolve
+
+    @property
+    def step_count(self) -> int:
+        """Optimizer steps APPLIED so far (skipped ones do not count): the AdamW bias-correction step and, times
+        lr_scheduler_steps_per_optimizer_step, the position of the LR schedule."""
+        self._resolve_verdict()
+        return self._step_count
+
+    @step_count.setter
+    def step_count(self, value):
+        self._resolve_verdict()
+        self._step_count = value
+
+    def _resolve_verdict(self):
+        """Waits for the EVENT behind the last verdict copy (not for the device) and takes a skipped step back out of the
+        host's count.  A no-op unless a guarded optimizer stage was issued since the last call."""
+        ev = self._pending
+        if ev is None:
+            return
+        self._pending = None
+        ev.synchronize()
+        skip, reason = (int(x) for x in self._verdict_host.tolist())
+        self._last_skipped, self._last_reason = bool(skip), SKIP_REASONS[reason]
+        if skip:
+            self._step_count -= 1
+            self._skipped += 1
+
+    @property
+    def skipped_steps(self) -> int:
+        """Optimizer steps dropped by the guard since construction (or since the checkpoint this trainer resumed)."""
+        self._resolve_verdict()
+        return self._skipped
+
+    @property
+    def last_step_skipped(self) -> bool:
+        self._resolve_verdict()
+        return self._last_skipped
+
+    @property
+    def last_skip_reason(self) -> Optional[str]:
+        """None (the last optimizer step was applied), "nonfinite" or "grad_norm"."""
+        self._resolve_verdict()
+        return self._last_reason
+
+    def _sumsq_order(self) -> List[_Bucket]:
+        """The buckets in the order their sums of squares are added: the layers, then the small bucket."""
+        return self.buckets[1:] + self.buckets[:1]
+
+    def bucket_grad_norms(self) -> Dict[object, float]:
+        """{bucket key: norm of what this rank's bucket (its shard when sharded) held at the last optimizer stage}, in the
+        order the sums are added (layers 0 .. L-1, then "small"; LoRA: "lora").  Each norm is the float64 square root of
+        the fp32 sum vgpt_sumsq_keep stored, so float32(norm ** 2) is that sum again and adding those in this order, in
+        fp32, gives trainer.sumsq bit for bit.  Needs skip_bad_steps=True (the unguarded step keeps no per-bucket sums)."""
+        if not self.skip_bad_steps:
+            raise VgptError("bucket_grad_norms: per-bucket sums are kept by the guarded step only (skip_bad_steps=True)")
+        parts = self._bucket_sumsq.tolist()
+        return {b.key: (math.sqrt(x) if x >= 0.0 else math.nan) for b, x in zip(self._sumsq_order(), parts)}
+
+    def nonfinite_report(self):
+        """[(parameter name, number of NaN, number of +-Inf), ...] of what this rank's gradient buckets hold NOW, tensors
+        with a non-zero count only (LoRA: the adapter slots, rank padding included), through vgpt_count_nonfinite with the
+        buckets' tensor offsets.  A diagnostic for after a skip: one pass over the buckets and a read-back."""
+        if not self.buckets:
+            raise VgptError("nonfinite_report: a forward-only trainer has no gradient buckets")
+        out = []
+        for b in self.buckets:
+            off = self._ws.get(("nf_off", b.key))
+            if off is None:
+                sizes = self._lora_sizes if b.key == "lora" else [self.params[k].numel() for k in b.names]
+                edges = [0]
+                for n in sizes:
+                    edges.append(edges[-1] + n)
+                off = self._ws[("nf_off", b.key)] = torch.tensor(edges, dtype=torch.int64, device=self.dev)
+            counts = T.count_nonfinite(b.grad, off).tolist()
+            out += [(k, n_nan, n_inf) for k, (n_nan, n_inf) in zip(b.names, counts) if n_nan or n_inf]
+        return out
+
     # ---- gradient accumulation ---------------------------------------------------------------------------------------
     def _accum_mode(self, update: bool):
         """None: no accumulation in this call (A == 1, or a stand-alone backward); else vgpt_grad_accumulate's mode of this
@@ -538,6 +663,10 @@ class Stage1Trainer:
         self.sumsq = torch.zeros(1, dtype=F32, device=self.dev)
         self.coef = torch.ones(1, dtype=F32, device=self.dev)
         self.grad_norm = torch.zeros(1, dtype=F32, device=self.dev)
+        if self.skip_bad_steps:
+            self._verdict = torch.zeros(2, dtype=torch.int32, device=self.dev)         # {skip?, reason}, written by the clip kernel
+            self._verdict_host = torch.zeros(2, dtype=torch.int32).pin_memory()
+            self._bucket_sumsq = torch.zeros(len(self.buckets), dtype=F32, device=self.dev)   # per bucket, _sumsq_order()
 
     # ---- dp_sharding="optimizer" -----------------------------------------------------------------------------------
     def _padded(self, n: int) -> int:
@@ -568,9 +697,12 @@ class Stage1Trainer:
                 w.wait()
 
     @classmethod
-    def for_evaluation(cls, model, deterministic: bool = False):
+    def for_evaluation(cls, model, deterministic: bool = False, skip_bad_steps: bool = False,
+                       skip_grad_norm_above: Optional[float] = None):
         """A forward-only trainer cached on the model (no gradient buckets, no optimizer state; `deterministic` is kept on
-        a new one and changes nothing: the forward pass has no order-dependent sum)."""
+        a new one and changes nothing: the forward pass has no order-dependent sum).  skip_bad_steps /
+        skip_grad_norm_above are refused: there is no optimizer step to guard."""
+        check_guard_arguments(skip_bad_steps, skip_grad_norm_above, forward_only=True)
         tr = getattr(model, "_vgpt_eval_trainer", None)
         if tr is None:
             tr = cls(model, forward_only=True, deterministic=deterministic)
@@ -1040,9 +1172,13 @@ class Stage1Trainer:
         lr = self.current_lr()
         self.last_lr = lr
         self.step_count += 1
+        guard = self.skip_bad_steps
         self.sumsq.zero_()
-        for b in self.buckets[1:] + self.buckets[:1]:      # layers, then the small bucket: the order of the fp32 sum
-            T.sumsq(self._shard(b.grad), self.sumsq)
+        for i, b in enumerate(self._sumsq_order()):        # layers, then the small bucket: the order of the fp32 sum
+            if guard:      # the same adds; the bucket's own sum is kept for bucket_grad_norms()
+                T.sumsq_keep(self._shard(b.grad), self.sumsq, self._bucket_sumsq[i:i + 1])
+            else:
+                T.sumsq(self._shard(b.grad), self.sumsq)
         partials = self.sumsq
         if self._sharded and not self.skip_allreduce:
             # every rank's sum over its reduced shards, in rank order, added on the device in a fixed order by clip_coef:
@@ -1051,7 +1187,19 @@ class Stage1Trainer:
         w = float(self.world // (self._sp["P"] if self._sp else 1) * micro_batches)     # data-parallel replicas x micro-batches
         # norm of the AVERAGED gradient = norm(sum)/world; coefficient already carries the 1/world factor (and 1/A, when the
         # buckets hold the sum over A micro-batches)
-        T.clip_coef(partials, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w)
+        if guard:
+            # the verdict comes from the sum every rank holds with the same bits (replicated and sequence parallel: the
+            # reduced buckets; sharded: every rank's partial in rank order), so all ranks skip together without a collective.
+            # Its copy to pinned memory and the event behind it are all the host ever waits for, a step from now
+            # (_resolve_verdict): the AdamW launches below read the verdict on the device.
+            T.clip_coef_guarded(partials, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w,
+                                (self.skip_grad_norm_above or 0.0) * w, self._verdict)
+            self._verdict_host.copy_(self._verdict, non_blocking=True)
+            self._pending = torch.cuda.Event()
+            self._pending.record(torch.cuda.current_stream())
+        else:
+            T.clip_coef(partials, self.coef, self.grad_norm, (self.max_grad_norm or 0.0) * w, 1.0 / w)
+        adamw = self._adamw_guarded if guard else self._adamw
         b1, b2 = self.betas
         # AdamW on this rank's shard of every bucket (the whole bucket when not sharded), sharded: the bucket's bf16 parameters
         # all-gathered in place right behind its update.  The small bucket goes first (embeddings, heads: read first), then
@@ -1069,8 +1217,8 @@ class Stage1Trainer:
         evs, works = [], []
         with torch.cuda.stream(self._opt_stream if ov else torch.cuda.current_stream()):
             for b in order:
-                self._adamw(b.master, self._shard(b.param), self._shard(b.grad), b.m, b.v, b.ema if self.use_ema else None,
-                            lr, b1, b2)      # `use_ema` stays the live switch: scripts/accum_ema_step_time.py flips it
+                adamw(b.master, self._shard(b.param), self._shard(b.grad), b.m, b.v, b.ema if self.use_ema else None,
+                      lr, b1, b2)      # `use_ema` stays the live switch: scripts/accum_ema_step_time.py flips it
                 if self._sharded:
                     works.append(None if self.skip_allreduce else
                                  SPM.all_gather_flat(self._shard(b.param), self._group, out=b.param, async_op=True))
@@ -1121,7 +1269,8 @@ class Stage1Trainer:
                        "betas": list(self.betas), "eps": self.eps, "lr_scheduler": self.lr_scheduler,
                        "lr_warmup_steps": self.lr_warmup_steps, "lr_num_training_steps": self.lr_num_training_steps,
                        "lr_num_cycles": self.lr_num_cycles, "lr_power": self.lr_power,
-                       "gradient_accumulation_steps": self.accum_steps, **mode}, f)
+                       "gradient_accumulation_steps": self.accum_steps, **mode,
+                       **({"skipped_steps": self.skipped_steps} if self.skip_bad_steps else {})}, f)
 
     # ---- EMA weights -------------------------------------------------------------------------------------------------
     def _ema_flat(self, t):
@@ -1294,6 +1443,9 @@ class Stage1Trainer:
 
     def _restore_record(self, st, restore_hyperparameters: bool) -> int:
         self.step_count = int(st["step_count"])
+        # the guard's record: kept by a guarded trainer, absent from (and ignored by) an unguarded one
+        self._skipped = int(st.get("skipped_steps", 0)) if self.skip_bad_steps else 0
+        self._last_skipped, self._last_reason = False, None
         self._micro = 0
         if restore_hyperparameters:
             self.lr, self.wd, self.eps = float(st["lr"]), float(st["weight_decay"]), float(st["eps"])
