@@ -418,6 +418,28 @@ int vgpt_sampler_set_timesteps(const float* sigma, const int32_t* step, int n_st
 int vgpt_euler_cfg_update(float* z, void* z_model, const void* pred, const float* sigma,
                           const int32_t* step, int n_steps, int n_frames, int64_t elems, int pred_type,
                           int use_cfg, float cfg_scale, void* stream);
+/* One update of the sampler state by the chosen ODE solver, on the operands of vgpt_euler_cfg_update (same x1->v
+ * conversion on the fp32 state, same CFG on the two halves, both halves moved by the guided velocity v_i).
+ * h_i = sigma[i+1] - sigma[i], i = *step unless stated.  v_hist: ((n_frames / (1 + use_cfg)), elems) fp32, the guided
+ * velocity of the step; may be null for VGPT_SOLVER_EULER only.
+ *   VGPT_SOLVER_EULER, stage 0: vgpt_euler_cfg_update itself (bit for bit).
+ *   VGPT_SOLVER_AB2, stage 0: z += h_i (v_i + h_i / (2 h_{i-1}) (v_i - v_hist)) for i >= 1, the Euler step for i = 0;
+ *     v_hist = v_i at every step.  No-op for *step outside [0, n_steps).
+ *   VGPT_SOLVER_HEUN, stage 0 (predictor): v_hist = v_i, z_model = bf16(z + h_i v_i), z untouched; at *step = n_steps - 1
+ *     (sigma[n_steps] = 1: the corrector's x1 conversion would divide by zero) a full Euler step.  No-op outside
+ *     [0, n_steps).
+ *   VGPT_SOLVER_HEUN, stage 1 (corrector), launched AFTER vgpt_sampler_advance with pred = the model's output on
+ *     z_model at sigma[*step]: i = *step - 1, z' = z + h_i v_hist (recomputed in fp32), v' from pred with z' and
+ *     sigma[i+1], z += h_i / 2 (v_hist + v'), z_model = bf16(z).  No-op for *step outside [1, n_steps).
+ * The step is read from device memory (capturable); a replay past the end of the table touches nothing.
+ * VGPT_ERR_INVALID (the offending value in the message): null pointer, unknown solver / stage, stage != 0 for a
+ * one-stage solver, odd n_frames with CFG, n_steps <= 0, unknown pred_type. */
+#define VGPT_SOLVER_EULER 0
+#define VGPT_SOLVER_AB2 1
+#define VGPT_SOLVER_HEUN 2
+int vgpt_sampler_update(float* z, void* z_model, const void* pred, float* v_hist, const float* sigma,
+                        const int32_t* step, int n_steps, int n_frames, int64_t elems, int pred_type, int use_cfg,
+                        float cfg_scale, int solver, int stage, void* stream);
 /* *step += 1 */
 int vgpt_sampler_advance(int32_t* step, void* stream);
 /* dst[l][0:slab_bytes] = src[*step][l][0:slab_bytes] for l < n_layers (step clamped to [0, n_steps)); all sizes and

@@ -19,6 +19,7 @@ ACT_SILU, ACT_GELU, ACT_GELU_TANH, ACT_NONE = 0, 1, 2, 3
 EPI_NONE, EPI_RESID, EPI_BIAS = 0, 1, 2
 MX8_EPI_NONE, MX8_EPI_RESID, MX8_EPI_ROPE, MX8_EPI_GATED = 0, 1, 2, 3
 PRED_V, PRED_X1 = 0, 1
+SOLVER_EULER, SOLVER_AB2, SOLVER_HEUN = 0, 1, 2
 FILTER_BOX, FILTER_BICUBIC = 0, 1
 
 _P = c_void_p
@@ -86,6 +87,7 @@ SIGNATURES = {
     "vgpt_final_layer_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _I64, c_float, _P]),
     "vgpt_sampler_set_timesteps": (c_int, [_P, _P, c_int, _P, c_int, _P]),
     "vgpt_euler_cfg_update": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _I64, c_int, c_int, c_float, _P]),
+    "vgpt_sampler_update": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _I64, c_int, c_int, c_float, c_int, c_int, _P]),
     "vgpt_sampler_advance": (c_int, [_P, _P]),
     "vgpt_sampler_copy_step_rows": (c_int, [_P, _P, _P, c_int, c_int, _I64, _I64, _I64, _I64, _P]),
     "vgpt_cast_f32_to_bf16": (c_int, [_P, _P, _I64, _P]),

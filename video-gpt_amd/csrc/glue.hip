@@ -271,6 +271,82 @@ __global__ __launch_bounds__(256) void euler_cfg_kernel(float* __restrict__ z, b
     }
 }
 
+// Second-order updates on the same state.  `vh` keeps the guided velocity of the step, one fp32 per element
+// of one CFG half.  MODE 0: ab2 (z += h_i (v_i + h_i / (2 h_{i-1}) (v_i - v_{i-1})), step 0 = Euler, vh written every step).
+// MODE 1: Heun predictor (vh = v_i, zm = bf16(z + h_i v_i), z untouched; at the last step, where sigma[i+1] = 1 and the
+// corrector's x1 conversion would divide by zero, a full Euler step).  MODE 2: Heun corrector, launched after the step
+// counter moved on: i = *step - 1, z' = z + h_i vh recomputed in fp32, v' from `pred` at sigma[i+1], z += h_i/2 (v_i + v').
+// Where an update degenerates to Euler (ab2's step 0, ab2 on an unchanged velocity, Heun's last step) it must give
+// euler_cfg_kernel's bits, and which a * b + c the compiler fuses there is its choice per kernel.  So contraction is off in
+// this kernel and every rounding is spelled out, in the sequence euler_cfg_kernel compiles to for gfx950: CFG combination
+// fused, the conditional half z + rn(h v) in two roundings, the unconditional half fma(h, v, z)
+// (tests/test_solver_kernels_gpu.py::test_euler_identities_bit_for_bit holds the two kernels together).
+template <int MODE>
+__global__ __launch_bounds__(256) void solver_update_kernel(float* __restrict__ z, bf16* __restrict__ zm,
+                                                            const bf16* __restrict__ pred, float* __restrict__ vh,
+                                                            const float* __restrict__ sigma,
+                                                            const int32_t* __restrict__ step, int n_steps, int n_frames,
+                                                            int64_t elems, int pred_type, int use_cfg, float cfg_scale) {
+#pragma clang fp contract(off)
+    const int st = *step;
+    // the corrector reads sigma[st - 1], sigma[st]; the others sigma[st], sigma[st + 1] (and ab2 sigma[st - 1] for st >= 1)
+    if (MODE == 2 ? (st < 1 || st >= n_steps) : (st < 0 || st >= n_steps)) return;
+    const int s0 = MODE == 2 ? st - 1 : st;
+    const float sg = sigma[s0], sg_next = sigma[s0 + 1];
+    const float dt = sg_next - sg;
+    const float inv = 1.0f / (1.0f - (MODE == 2 ? sg_next : sg));   // x1 -> v at the sigma the prediction was made at
+    const bool two_step = MODE == 0 && st >= 1;
+    const float ratio = two_step ? 0.5f * dt / (sg - sigma[st - 1]) : 0.f;
+    const bool euler_tail = MODE == 1 && st == n_steps - 1;
+    const int half = use_cfg ? n_frames / 2 : n_frames;
+    const int64_t total = (int64_t)half * elems;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t iu = i + total;
+        float zc = z[i], zu = use_cfg ? z[iu] : 0.f;
+        float v0 = 0.f;
+        float zpc = zc, zpu = zu;   // the state the prediction was made from
+        if (MODE == 2) {
+            v0 = vh[i];
+            zpc = __builtin_fmaf(dt, v0, zc);   // as the predictor computed it before rounding it to bf16
+            zpu = __builtin_fmaf(dt, v0, zu);
+        }
+        float vc = bf2f(pred[i]);
+        if (pred_type == VGPT_PRED_X1) vc = (vc - zpc) * inv;
+        if (use_cfg) {
+            float vu = bf2f(pred[iu]);
+            if (pred_type == VGPT_PRED_X1) vu = (vu - zpu) * inv;
+            vc = __builtin_fmaf(cfg_scale, vc - vu, vu);
+        }
+        if (MODE == 0) {
+            float ve = vc;
+            if (two_step) ve = __builtin_fmaf(ratio, vc - vh[i], vc);
+            vh[i] = vc;
+            zc = zc + dt * ve;
+            zu = __builtin_fmaf(dt, ve, zu);
+        } else if (MODE == 1) {
+            if (!euler_tail) {
+                vh[i] = vc;
+                zm[i] = f2bf(__builtin_fmaf(dt, vc, zc));
+                if (use_cfg) zm[iu] = f2bf(__builtin_fmaf(dt, vc, zu));
+                continue;
+            }
+            zc = zc + dt * vc;
+            zu = __builtin_fmaf(dt, vc, zu);
+        } else {
+            const float hh = 0.5f * dt, vs = v0 + vc;
+            zc = __builtin_fmaf(hh, vs, zc);
+            zu = __builtin_fmaf(hh, vs, zu);
+        }
+        z[i] = zc;
+        zm[i] = f2bf(zc);
+        if (use_cfg) {
+            z[iu] = zu;
+            zm[iu] = f2bf(zu);
+        }
+    }
+}
+
 __global__ void advance_kernel(int32_t* step) { *step += 1; }
 
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ src,
@@ -411,6 +487,43 @@ VGPT_EXPORT int vgpt_euler_cfg_update(float* z, void* z_model, const void* pred,
                        (bf16*)z_model, (const bf16*)pred, sigma, step, n_steps, n_frames, elems, pred_type,
                        use_cfg, cfg_scale);
     VGPT_CHECK_LAUNCH("vgpt_euler_cfg_update");
+    return VGPT_OK;
+}
+
+VGPT_EXPORT int vgpt_sampler_update(float* z, void* z_model, const void* pred, float* v_hist, const float* sigma,
+                                    const int32_t* step, int n_steps, int n_frames, int64_t elems, int pred_type,
+                                    int use_cfg, float cfg_scale, int solver, int stage, void* stream) {
+    VGPT_REQUIRE(solver == VGPT_SOLVER_EULER || solver == VGPT_SOLVER_AB2 || solver == VGPT_SOLVER_HEUN, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update: unknown solver %d", solver);
+    VGPT_REQUIRE(stage == 0 || stage == 1, VGPT_ERR_INVALID, "vgpt_sampler_update: unknown stage %d", stage);
+    VGPT_REQUIRE(stage == 0 || solver == VGPT_SOLVER_HEUN, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update: stage %d of the one-stage solver %d", stage, solver);
+    VGPT_REQUIRE(z && z_model && pred && sigma && step, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update: null pointer (z %p, z_model %p, pred %p, sigma %p, step %p)", (void*)z, z_model, pred,
+                 (const void*)sigma, (const void*)step);
+    VGPT_REQUIRE(v_hist || solver == VGPT_SOLVER_EULER, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update: null v_hist with solver %d (only Euler keeps no history)", solver);
+    VGPT_REQUIRE(n_steps > 0, VGPT_ERR_INVALID, "vgpt_sampler_update: n_steps %d <= 0", n_steps);
+    VGPT_REQUIRE(n_frames >= 0 && elems >= 0, VGPT_ERR_INVALID, "vgpt_sampler_update: bad shape (%d frames of %lld)",
+                 n_frames, (long long)elems);
+    VGPT_REQUIRE(pred_type == VGPT_PRED_V || pred_type == VGPT_PRED_X1, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update: unknown prediction type %d", pred_type);
+    VGPT_REQUIRE(!use_cfg || n_frames % 2 == 0, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update: CFG needs an even number of frames (got %d)", n_frames);
+    if (solver == VGPT_SOLVER_EULER)   // the Euler kernel itself: its bits by construction
+        return vgpt_euler_cfg_update(z, z_model, pred, sigma, step, n_steps, n_frames, elems, pred_type, use_cfg, cfg_scale,
+                                     stream);
+    if (n_frames == 0 || elems == 0) return VGPT_OK;
+    const int64_t total = (int64_t)(use_cfg ? n_frames / 2 : n_frames) * elems;
+    int grid = (int)std::min<int64_t>(cdiv(total, 256), 2048);
+#define SU_LAUNCH(MODE)                                                                                              \
+    hipLaunchKernelGGL(solver_update_kernel<MODE>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, (bf16*)z_model, \
+                       (const bf16*)pred, v_hist, sigma, step, n_steps, n_frames, elems, pred_type, use_cfg, cfg_scale)
+    if (solver == VGPT_SOLVER_AB2) SU_LAUNCH(0);
+    else if (stage == 0) SU_LAUNCH(1);
+    else SU_LAUNCH(2);
+#undef SU_LAUNCH
+    VGPT_CHECK_LAUNCH("vgpt_sampler_update");
     return VGPT_OK;
 }
 

@@ -141,7 +141,10 @@ class StaticDenoiser:
                  prediction_type: str = "v", sigma: Optional[torch.Tensor] = None, pack_padding: bool = True,
                  reuse_condition_prefix: bool = False, hoist_special_rows: bool = True,
                  attention_precision: str = "bf16", fuse_norms: Optional[bool] = None, linear_precision: str = "bf16",
-                 sequence_parallel: bool = False, sp_group=None):
+                 sequence_parallel: bool = False, sp_group=None, solver: str = "euler"):
+        # solver: "euler" (default), "ab2" or "heun" (DESIGN.md section 5); an unknown name is refused, naming it, before
+        # anything else is looked at
+        self.solver = ops.solver_id(solver)
         model._check_ready()
         # fuse_norms: the two RMSNorms of a decoder layer folded into the GEMMs around them in the per-step forward (ops:
         # linear_resid_ssq -> *_prenorm; include/vgpt.h).  None = on wherever the step's shapes allow it, VGPT_FUSE_NORMS=0
@@ -319,6 +322,10 @@ class StaticDenoiser:
         self.z = e(n_frames, C * self.h * self.w, dt=torch.float32)
         self.z_model = e(n_frames, C, self.h, self.w)
         self.pred = e(n_frames, C, self.h, self.w)
+        # ab2 / heun: the guided velocity of the step, one CFG half.  Never cleared between clips: step 0 writes it before
+        # anything reads it (ab2 reads from step 1 on, the Heun corrector after its own predictor)
+        self.v_hist = None if self.solver == ops.SOLVER_EULER else e(n_frames // (2 if self.use_cfg else 1),
+                                                                     C * self.h * self.w, dt=torch.float32)
         self.ts = e(n_frames, dt=torch.float32)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
         self.sigma = None
@@ -377,7 +384,7 @@ class StaticDenoiser:
         self.te_h = e(n_frames, H)
         self.temb = e(n_frames, H)
         self.mod = e(n_frames, 2 * H)
-        self.graph = None
+        self.graph = self.graph_last = None
         self.time_qkv = None   # hoisting: (steps, layers, n_frames, 3H) q/k/v rows of the time tokens of every step
         self.mod_all = None    # (steps, 1, n_frames, 2H) adaLN shift / scale of the final layer for every step (_mod_pass)
         self.steps_taken = 0
@@ -544,7 +551,7 @@ class StaticDenoiser:
         wq, wgu = folded_weights(self.model)
         if wq is not self.fuse["wq"] or wgu is not self.fuse["wgu"]:   # re-allocated (other shapes): the graph read the old ones
             self.fuse["wq"], self.fuse["wgu"] = wq, wgu
-            self.graph = None
+            self.graph = self.graph_last = None
 
     def quantize_weights(self):
         """linear_precision "fp8": every decoder layer's qkv / o / gate_up / down weights into their MX-fp8 records, from the
@@ -578,7 +585,7 @@ class StaticDenoiser:
         shape = (T, 1, self.nf, 2 * H)
         if self.mod_all is None or tuple(self.mod_all.shape) != shape:
             self.mod_all = e(*shape)          # a captured graph reads this buffer: re-allocating invalidates it
-            self.graph = None
+            self.graph = self.graph_last = None
         self.mod_all.copy_(mod.view(T, 1, 1, 2 * H).expand(*shape))
 
     # ---- special-row hoisting ------------------------------------------------------------------------------------
@@ -661,7 +668,7 @@ class StaticDenoiser:
         shape = (T, self.cfg.num_hidden_layers, nf, W)
         if self.time_qkv is None or tuple(self.time_qkv.shape) != shape:
             self.time_qkv = e(*shape)      # a captured graph reads this buffer: re-allocating invalidates it
-            self.graph = None
+            self.graph = self.graph_last = None
         seg = ((0, 0, Lp),)
 
         def keep(li):
@@ -860,30 +867,61 @@ class StaticDenoiser:
         self._layers(self.hid, self.nrm, ctx, self.act, rope, qkv_dst, attention, fz=self.fuse, mx=self.mx8)
         self._step_tail(from_tables)
 
-    def sampler_step(self):
-        """LVM/scheduler.py:168-204 for one i: timesteps, model call, x1->v, CFG, Euler, i += 1."""
+    def sampler_step(self, last: bool = True):
+        """LVM/scheduler.py:168-204 for one i: timesteps, model call, x1->v, CFG, update, i += 1.  Euler and ab2: one model
+        call and one update kernel.  Heun (`last` False: not the final step of the table): model call, predictor, i += 1,
+        model call at sigma[i+1] on bf16(z + h v), corrector -- the step tables are read by *step, so the second call reads
+        index i + 1 <= N - 1; the final step (sigma[N] = 1) is the Euler-shaped one."""
         ops.sampler_set_timesteps(self.sigma, self.step, self.ts)
         self.forward_step(from_tables=True)
-        ops.euler_cfg_update(self.z, self.z_model, self.pred, self.sigma, self.step, self.pred_type, self.use_cfg,
-                             self.cfg_scale)
+        upd = (self.z, self.z_model, self.pred, self.v_hist, self.sigma, self.step, self.pred_type, self.use_cfg,
+               self.cfg_scale)
+        if self.solver == ops.SOLVER_HEUN and not last:
+            ops.sampler_update(*upd, ops.SOLVER_HEUN, 0)
+            ops.sampler_advance(self.step)
+            ops.sampler_set_timesteps(self.sigma, self.step, self.ts)
+            self.forward_step(from_tables=True)
+            ops.sampler_update(*upd, ops.SOLVER_HEUN, 1)
+            return
+        if self.solver == ops.SOLVER_AB2:
+            ops.sampler_update(*upd, ops.SOLVER_AB2)
+        else:
+            ops.euler_cfg_update(self.z, self.z_model, self.pred, self.sigma, self.step, self.pred_type, self.use_cfg,
+                                 self.cfg_scale)
         ops.sampler_advance(self.step)
 
-    def _step_then_capture(self, restore: bool):
+    def _step_then_capture(self, restore: bool, last: bool = True):
         """One eager step (kernels set their launch attributes on first use, which a capture cannot record), then the capture
-        of a step, which records without executing.  restore: the eager step leaves no trace in the sampler state."""
+        of a step, which records without executing.  restore: the eager step leaves no trace in the sampler state (the
+        velocity history included: an ab2 step in the middle of a clip reads what the step before it wrote).  Heun keeps two graphs: the
+        two-call step (`graph`) and the Euler-shaped final step (`graph_last`); the other solvers have `graph` alone."""
         saved = (self.z.clone(), self.z_model.clone(), self.step.clone()) if restore else None
-        self.sampler_step()
+        hist = self.v_hist.clone() if restore and self.v_hist is not None else None
+        self.sampler_step(last)
         torch.cuda.current_stream().synchronize()
         if restore:
             self.z.copy_(saved[0]); self.z_model.copy_(saved[1]); self.step.copy_(saved[2])
+            if hist is not None:
+                self.v_hist.copy_(hist)
             torch.cuda.current_stream().synchronize()
-        self.graph = ops.HipGraph().capture(self.sampler_step)
+        graph = ops.HipGraph().capture(lambda: self.sampler_step(last))
+        if self._two_graphs() and last:
+            self.graph_last = graph
+        else:
+            self.graph = graph
+
+    def _two_graphs(self) -> bool:
+        return self.solver == ops.SOLVER_HEUN
+
+    def _is_last(self, index: int) -> bool:
+        """Whether step `index` of the table takes the Euler-shaped step: every step of the one-call solvers, Heun's final one."""
+        return not self._two_graphs() or index == self.num_steps - 1
 
     def capture(self):
         """Capture one sampler step into a hipGraph (must run on a non-default stream)."""
         if self.sp is not None:
             raise VgptError("StaticDenoiser.capture: a sequence-parallel engine runs eagerly (its exchanges are not captured)")
-        self._step_then_capture(restore=True)
+        self._step_then_capture(restore=True, last=self._is_last(self.steps_taken))
         return self
 
     def run(self, num_steps: Optional[int] = None, use_graph: bool = True):
@@ -891,14 +929,17 @@ class StaticDenoiser:
         if self.steps_taken + n > self.num_steps:
             raise VgptError(f"StaticDenoiser.run: {n} more steps after {self.steps_taken} exceed the {self.num_steps}-step "
                             "sigma table")
+        first = self.steps_taken
         self.steps_taken += n
         use_graph = use_graph and self.sp is None   # sharded engines run eagerly: collectives are not captured (yet)
-        if use_graph and self.graph is None and n > 0:
-            self._step_then_capture(restore=False)   # the eager step counts as a real one
-            n -= 1
-        for _ in range(n):
-            if use_graph:
-                self.graph.replay()
+        for index in range(first, first + n):
+            last = self._is_last(index)   # by the absolute index: run(k) then run(N - k) is run(N)
+            if not use_graph:
+                self.sampler_step(last)
+                continue
+            graph = self.graph_last if self._two_graphs() and last else self.graph
+            if graph is None:
+                self._step_then_capture(restore=False, last=last)   # the eager step counts as a real one
             else:
-                self.sampler_step()
+                graph.replay()
         return self.z

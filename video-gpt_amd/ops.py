@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_GELU, ACT_GELU_TANH, ACT_NONE, ACT_SILU, EPI_BIAS, EPI_NONE, EPI_RESID,
-                   PRED_V, PRED_X1, VgptError, call)
+                   PRED_V, PRED_X1, SOLVER_AB2, SOLVER_EULER, SOLVER_HEUN, VgptError, call)
 
 BF16 = torch.bfloat16
 
@@ -882,6 +882,35 @@ def euler_cfg_update(z: torch.Tensor, z_model: torch.Tensor, pred: torch.Tensor,
     nf = z.shape[0]
     call("vgpt_euler_cfg_update", z.data_ptr(), z_model.data_ptr(), pred.data_ptr(), sigma.data_ptr(),
          step.data_ptr(), sigma.numel() - 1, nf, z.numel() // nf, pred_type, int(use_cfg), float(cfg_scale), _stream())
+
+
+SOLVERS = {"euler": SOLVER_EULER, "ab2": SOLVER_AB2, "heun": SOLVER_HEUN}
+
+
+def solver_id(solver: str) -> int:
+    if solver not in SOLVERS:
+        raise VgptError(f"unknown sampler solver {solver!r} (one of {sorted(SOLVERS)})")
+    return SOLVERS[solver]
+
+
+def sampler_update(z: torch.Tensor, z_model: torch.Tensor, pred: torch.Tensor, v_hist: Optional[torch.Tensor],
+                   sigma: torch.Tensor, step: torch.Tensor, pred_type: int, use_cfg: bool, cfg_scale: float,
+                   solver: int = SOLVER_EULER, stage: int = 0):
+    """One solver update of the fp32 state (include/vgpt.h: vgpt_sampler_update).  v_hist: fp32, one CFG half of z (all of
+    z without CFG); None for Euler only.  Heun: stage 0 before, stage 1 after sampler_advance()."""
+    _chk(z, torch.float32, "sampler_update.z"); _chk(z_model, BF16, "sampler_update.z_model")
+    _chk(pred, BF16, "sampler_update.pred")
+    nf = z.shape[0]
+    if z_model.numel() != z.numel() or pred.numel() != z.numel():
+        raise VgptError(f"sampler_update: z_model ({z_model.numel()}) / pred ({pred.numel()}) are not z's {z.numel()} elements")
+    if v_hist is not None:
+        _chk(v_hist, torch.float32, "sampler_update.v_hist")
+        need = z.numel() // (2 if use_cfg else 1)
+        if v_hist.numel() != need:
+            raise VgptError(f"sampler_update: v_hist holds {v_hist.numel()} values, the guided velocity has {need}")
+    call("vgpt_sampler_update", z.data_ptr(), z_model.data_ptr(), pred.data_ptr(), _ptr(v_hist), sigma.data_ptr(),
+         step.data_ptr(), sigma.numel() - 1, nf, z.numel() // max(nf, 1), pred_type, int(use_cfg), float(cfg_scale),
+         int(solver), int(stage), _stream())
 
 
 def sampler_copy_step_rows(src: torch.Tensor, dst: torch.Tensor, step: torch.Tensor):

@@ -43,6 +43,7 @@ class LVMPipeline:
         self.attention_precision = "bf16"   # "fp8": MX-fp8 attention in the sampler steps (scheduler.LVMScheduler)
         self.linear_precision = "bf16"      # "fp8": MX-fp8 decoder-layer projections in the sampler steps (scheduler.LVMScheduler)
         self.sequence_parallel_engine = False   # True: sharded sampler engine under a sequence-parallel group (scheduler.LVMScheduler)
+        self.solver = "euler"               # "ab2" / "heun": second-order sampler steps (scheduler.LVMScheduler)
 
     @classmethod
     def from_pretrained(cls, model_name, vae_path: str = None, load_llm_ckpt=True):
@@ -199,7 +200,8 @@ class LVMPipeline:
                                 position_ids=self.move_to_device(input_data["position_ids"]),
                                 img_cfg_scale=img_guidance_scale, use_img_cfg=use_img_guidance, use_kv_cache=use_kv_cache,
                                 offload_model=False)
-            scheduler = LVMScheduler(num_steps=num_inference_steps, time_shifting_factor=time_shifting_factor)
+            scheduler = LVMScheduler(num_steps=num_inference_steps, time_shifting_factor=time_shifting_factor,
+                                     solver=self.solver)
             scheduler.attention_precision = self.attention_precision
             scheduler.linear_precision = self.linear_precision
             scheduler.sequence_parallel_engine = self.sequence_parallel_engine
@@ -307,7 +309,8 @@ class LVMPipeline:
                 denoise_image_sizes=input_data["denoise_image_sizes"], time_emb_inx=input_data["time_emb_inx"],
                 img_cfg_scale=img_guidance_scale, use_img_cfg=use_img_guidance, use_kv_cache=use_kv_cache,
                 offload_model=False, vae=self.vae)
-            scheduler = LVMScheduler(num_steps=num_inference_steps, time_shifting_factor=time_shifting_factor)
+            scheduler = LVMScheduler(num_steps=num_inference_steps, time_shifting_factor=time_shifting_factor,
+                                     solver=self.solver)
             scheduler.attention_precision = self.attention_precision
             scheduler.linear_precision = self.linear_precision
             scheduler.sequence_parallel_engine = self.sequence_parallel_engine

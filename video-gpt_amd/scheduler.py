@@ -1,4 +1,6 @@
-"""LVMScheduler: Euler rectified-flow sampler (mirror of LVM/scheduler.py:119-208).
+"""LVMScheduler: rectified-flow sampler (mirror of LVM/scheduler.py:119-208: first-order Euler, the default), with two
+second-order solvers beside it (`solver="ab2"`: two-step Adams-Bashforth, one model call per step; `solver="heun"`:
+2 N - 1 model calls for N steps; arithmetic in DESIGN.md section 5).
 
 `__call__(z, func, model_kwargs, ...)` keeps the reference contract:
 `func(z, timesteps, past_key_values=None, prediction_type=..., **model_kwargs) -> (pred, cache)`.
@@ -26,7 +28,9 @@ from .ops import BF16, VgptError
 
 
 class LVMScheduler:
-    def __init__(self, num_steps: int = 50, time_shifting_factor: int = 1, begin_time=None):
+    def __init__(self, num_steps: int = 50, time_shifting_factor: int = 1, begin_time=None, solver: str = "euler"):
+        ops.solver_id(solver)   # an unknown name is refused here, naming it
+        self.solver = solver
         self.num_steps = num_steps
         self.time_shift = time_shifting_factor
         t = torch.linspace(0 if begin_time is None else begin_time, 1, num_steps + 1)
@@ -100,7 +104,7 @@ class LVMScheduler:
                 len(z), tuple(z[0].shape), None if not lat else (len(lat), tuple(lat[0].shape)),
                 bool(model_kwargs["use_img_cfg"]), float(model_kwargs["img_cfg_scale"]), prediction_type, tb(self.sigma),
                 self.pack_padding, self.reuse_condition_prefix, self.hoist_special_rows, self.attention_precision,
-                self.linear_precision, self.fuse_norms, str(z[0].device),
+                self.linear_precision, self.fuse_norms, str(z[0].device), self.solver,
                 # a sharded engine holds this rank's rows and heads of a group of this size
                 self.sequence_parallel_engine, SPM.sp_world(), SPM.sp_rank(),
                 # the GEMM family decided whether the engine folded the RMSNorms (norm_workspace_bytes is 0 under family 1) and
@@ -119,7 +123,8 @@ class LVMScheduler:
                               reuse_condition_prefix=self.reuse_condition_prefix,
                               hoist_special_rows=self.hoist_special_rows,
                               attention_precision=self.attention_precision, linear_precision=self.linear_precision,
-                              fuse_norms=self.fuse_norms, sequence_parallel=self.sequence_parallel_engine)
+                              fuse_norms=self.fuse_norms, sequence_parallel=self.sequence_parallel_engine,
+                              solver=self.solver)
 
     def __call__(self, z, func, model_kwargs, use_kv_cache: bool = True, offload_kv_cache: bool = True,
                  prediction_type: str = "v", vae=None, noise_level=None):
@@ -188,15 +193,32 @@ class LVMScheduler:
         kernel_cfg = use_cfg and prediction_type == "x1"
         if kernel_cfg and n % 2:
             raise VgptError("image CFG needs the conditional and unconditional halves (an even number of latents)")
-        for _ in range(self.num_steps):
+        pred_type = ops.PRED_X1 if prediction_type == "x1" else ops.PRED_V
+        solver = ops.solver_id(self.solver)
+        # the guided velocity of the step (ab2: of the previous one when it is read), one CFG half
+        v_hist = None if solver == ops.SOLVER_EULER else torch.empty(n // 2 if kernel_cfg else n, elems, dtype=torch.float32,
+                                                                    device=dev)
+
+        def evaluate():
             ops.sampler_set_timesteps(sigma, step, ts)
             z_in = [zm[i].view(shapes[i]) for i in range(n)] if is_list else zm.view(frames[0].shape)
             pred, _cache = func(z_in, ts, past_key_values=None, prediction_type=prediction_type, **model_kwargs)
             if is_list:
                 pred = torch.cat([p.reshape(1, -1) for p in pred], dim=0)
-            pred = pred.reshape(n, elems).to(BF16).contiguous()
-            ops.euler_cfg_update(zf, zm, pred, sigma, step, ops.PRED_X1 if prediction_type == "x1" else ops.PRED_V,
-                                 kernel_cfg, scale)
+            return pred.reshape(n, elems).to(BF16).contiguous()
+
+        for i in range(self.num_steps):
+            pred = evaluate()
+            if solver == ops.SOLVER_HEUN and i < self.num_steps - 1:
+                # predictor -> the model at sigma[i+1] on bf16(z + h v) -> corrector; the last step (sigma = 1) is Euler's
+                ops.sampler_update(zf, zm, pred, v_hist, sigma, step, pred_type, kernel_cfg, scale, solver, 0)
+                ops.sampler_advance(step)
+                ops.sampler_update(zf, zm, evaluate(), v_hist, sigma, step, pred_type, kernel_cfg, scale, solver, 1)
+                continue
+            if solver == ops.SOLVER_AB2:
+                ops.sampler_update(zf, zm, pred, v_hist, sigma, step, pred_type, kernel_cfg, scale, solver)
+            else:
+                ops.euler_cfg_update(zf, zm, pred, sigma, step, pred_type, kernel_cfg, scale)
             ops.sampler_advance(step)
         out = zf.to(out_dtype)
         if is_list:
