@@ -368,7 +368,8 @@ int vgpt_attn_set_hand_scheduled(int on);
 
 /* ---- model glue ---------------------------------------------------------- */
 
-/* embed_tokens gather (LVM/model.py:430-432): out[r] = table[ids[r]]. H % 8 == 0. */
+/* embed_tokens gather (LVM/model.py:430-432): out[r] = table[ids[r]]. H % 8 == 0.
+ * An id outside [0, vocab) is clamped to the nearest valid row (0 or vocab - 1): no read leaves the table. */
 int vgpt_embed_gather(const int64_t* ids, const void* table, void* out, int64_t rows, int64_t H,
                       int64_t vocab, void* stream);
 
@@ -391,7 +392,8 @@ int vgpt_timestep_sinusoid(const float* t, const float* freqs, void* out, int n,
  * pre/post: VGPT_ACT_NONE or VGPT_ACT_SILU. Replaces the TimestepEmbedder MLP
  * (LVM/model.py:32-36) and FinalLayer.adaLN_modulation (LVM/model.py:74-77).
  * out rows may be scattered: row m is written at out + out_row[m]*ldo when out_row != NULL
- * (time tokens scattered into the sequence, LVM/model.py:442-446). K % 8 == 0. */
+ * (time tokens scattered into the sequence, LVM/model.py:442-446). K % 8 == 0, ldx % 8 == 0,
+ * ldx >= K and ldo >= N (row strides in elements). */
 int vgpt_linear_small(const void* x, const void* W, const void* bias, void* out,
                       const int32_t* out_row, int M, int64_t N, int64_t K, int64_t ldx, int64_t ldo,
                       int pre_act, int post_act, void* stream);

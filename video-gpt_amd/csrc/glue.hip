@@ -363,6 +363,7 @@ VGPT_EXPORT int vgpt_embed_gather(const int64_t* ids, const void* table, void* o
     VGPT_REQUIRE(ids && table && out, VGPT_ERR_INVALID, "vgpt_embed_gather: null pointer");
     VGPT_REQUIRE(rows >= 0 && H > 0 && vocab > 0, VGPT_ERR_INVALID, "vgpt_embed_gather: bad shape");
     VGPT_REQUIRE(H % 8 == 0, VGPT_ERR_UNSUPPORTED, "vgpt_embed_gather: H must be a multiple of 8");
+    VGPT_REQUIRE(H < (1ll << 31), VGPT_ERR_UNSUPPORTED, "vgpt_embed_gather: H=%lld too large", (long long)H);
     if (rows == 0) return VGPT_OK;
     int grid = (int)std::min<int64_t>(cdiv(rows * (H / 8), 256), (int64_t)1 << 30);
     hipLaunchKernelGGL(embed_gather_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, ids,
@@ -382,6 +383,7 @@ VGPT_EXPORT int vgpt_patch_embed_fwd(const void* x, const void* Wp, const void* 
     VGPT_REQUIRE(C * 4 == 16 && h % 2 == 0 && w % 2 == 0, VGPT_ERR_UNSUPPORTED,
                  "vgpt_patch_embed_fwd: needs in_channels=4, patch 2, even latent size");
     VGPT_REQUIRE(H % 4 == 0, VGPT_ERR_UNSUPPORTED, "vgpt_patch_embed_fwd: H must be a multiple of 4");
+    VGPT_REQUIRE(H < (1ll << 31), VGPT_ERR_UNSUPPORTED, "vgpt_patch_embed_fwd: H=%lld too large", (long long)H);
     VGPT_REQUIRE(h / 2 <= pos_max && w / 2 <= pos_max, VGPT_ERR_INVALID,
                  "vgpt_patch_embed_fwd: latent larger than pos_embed_max_size");
     if (n_frames == 0) return VGPT_OK;
@@ -414,6 +416,8 @@ VGPT_EXPORT int vgpt_linear_small(const void* x, const void* W, const void* bias
                  "vgpt_linear_small: K and ldx must be multiples of 8");
     VGPT_REQUIRE(N < (1ll << 31) && K < (1ll << 31), VGPT_ERR_UNSUPPORTED,
                  "vgpt_linear_small: dimension too large");
+    VGPT_REQUIRE(ldx >= K, VGPT_ERR_INVALID, "vgpt_linear_small: ldx=%lld < K=%lld", (long long)ldx, (long long)K);
+    VGPT_REQUIRE(ldo >= N, VGPT_ERR_INVALID, "vgpt_linear_small: ldo=%lld < N=%lld", (long long)ldo, (long long)N);
     if (M == 0) return VGPT_OK;
     int grid = (int)std::min<int64_t>(cdiv(N, 4), 256 * 8);
     hipStream_t s = (hipStream_t)stream;

@@ -228,7 +228,7 @@ VGPT_EXPORT int vgpt_attn_qblock_order(const uint8_t* summary, int64_t B, int64_
 VGPT_EXPORT int vgpt_mask_count_empty_rows(const uint32_t* bits, int32_t* count, int64_t B,
                                            int64_t L, void* stream) {
     VGPT_REQUIRE(bits && count, VGPT_ERR_INVALID, "vgpt_mask_count_empty_rows: null pointer");
-    VGPT_REQUIRE(B >= 0 && L >= 0, VGPT_ERR_INVALID, "vgpt_mask_count_empty_rows: bad shape");
+    VGPT_REQUIRE(B >= 0 && L >= 0 && L < (1 << 24), VGPT_ERR_INVALID, "vgpt_mask_count_empty_rows: bad shape");
     hipError_t e = hipMemsetAsync(count, 0, sizeof(int32_t), (hipStream_t)stream);
     if (e != hipSuccess) {
         vgpt_set_error("vgpt_mask_count_empty_rows: memset: %s", hipGetErrorString(e));

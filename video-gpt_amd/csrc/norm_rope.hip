@@ -93,6 +93,7 @@ VGPT_EXPORT int vgpt_rmsnorm_fwd(const void* x, const void* w, void* y, int64_t 
     VGPT_REQUIRE(rows >= 0 && H > 0, VGPT_ERR_INVALID, "vgpt_rmsnorm_fwd: bad shape");
     VGPT_REQUIRE(H % 8 == 0, VGPT_ERR_UNSUPPORTED, "vgpt_rmsnorm_fwd: H=%ld not a multiple of 8",
                  (long)H);
+    VGPT_REQUIRE(H < (1ll << 31), VGPT_ERR_UNSUPPORTED, "vgpt_rmsnorm_fwd: H=%lld too large", (long long)H);
     if (rows == 0) return VGPT_OK;
     hipStream_t s = (hipStream_t)stream;
     int grid = (int)std::min<int64_t>(cdiv(rows, 4), 256 * 8);
@@ -237,6 +238,7 @@ VGPT_EXPORT int vgpt_rms_rstd(const void* x, float* rstd_out, int64_t rows, int6
                  "vgpt_rms_rstd: H and ldx must be multiples of 8, ldx >= H");
     VGPT_REQUIRE(rows == 0 || (x && rstd_out), VGPT_ERR_INVALID, "vgpt_rms_rstd: null pointer");
     VGPT_REQUIRE(((uintptr_t)x & 15) == 0, VGPT_ERR_UNSUPPORTED, "vgpt_rms_rstd: rows must be 16-byte aligned");
+    VGPT_REQUIRE(H < (1ll << 31), VGPT_ERR_UNSUPPORTED, "vgpt_rms_rstd: H=%lld too large", (long long)H);
     if (rows == 0) return VGPT_OK;
     const int blocks = (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);
     hipLaunchKernelGGL(rms_rstd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, rstd_out, rows, (int)H, ldx, eps);
@@ -263,6 +265,7 @@ VGPT_EXPORT int vgpt_fold_norm_gain(const void* W, const void* gain, void* W_out
     VGPT_REQUIRE(N == 0 || (W && gain && W_out), VGPT_ERR_INVALID, "vgpt_fold_norm_gain: null pointer");
     VGPT_REQUIRE((((uintptr_t)W | (uintptr_t)gain | (uintptr_t)W_out) & 15) == 0, VGPT_ERR_UNSUPPORTED,
                  "vgpt_fold_norm_gain: operands must be 16-byte aligned");
+    VGPT_REQUIRE(K < (1ll << 31), VGPT_ERR_UNSUPPORTED, "vgpt_fold_norm_gain: K=%lld too large", (long long)K);
     if (N == 0) return VGPT_OK;
     const int64_t n_vec = N * K / 8;
     hipLaunchKernelGGL(fold_gain_kernel, dim3((unsigned)((n_vec + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)W,
