@@ -3,7 +3,7 @@
 CPU: its dense expansion equals, bit for bit, the masks dumped from the REFERENCE'S OWN collator
 (tests/golden/ref_collator_*.npz) for all three layouts, and its re-layouts (dropping left pads and concatenating the
 rows; the alignment gap behind the condition prefix) equal the same operations done on the dense tensors
-(engine.pack_left_padded / StaticDenoiser).  GPU: the device expansion (vgpt_mask_build_tokens) equals the packed
+(step_plan.pack_left_padded / plan_step_rows).  GPU: the device expansion (vgpt_mask_build_tokens) equals the packed
 rows of the dense mask, bit for bit, and the sampler gives the same latents from either form."""
 import glob
 import importlib
@@ -17,6 +17,7 @@ from tests.test_collator import GOLD, load, product_fbtrain, product_inference, 
 
 LY = importlib.import_module("video-gpt_amd.layout")
 E = importlib.import_module("video-gpt_amd.engine")
+SP = importlib.import_module("video-gpt_amd.step_plan")
 
 
 def names(pat):
@@ -153,7 +154,7 @@ def test_device_expansion_cfg4_shape_properties(ops):
 
 
 def test_hoist_plan_permutation_matches_dense_permutation():
-    """engine.StaticDenoiser._hoist_plan: the re-ordering [prefix | <|diffusion|> rows | time rows | gap | image rows] of
+    """step_plan._hoist_plan: the re-ordering [prefix | <|diffusion|> rows | time rows | gap | image rows] of
     a packed next-clip sequence is a pure permutation of tokens: the permuted layout expands to the dense mask with
     rows and columns permuted (gap rows / columns empty), and every frame's rows land where the plan says."""
     C, G, N = 2, 3, 16
@@ -163,7 +164,7 @@ def test_hoist_plan_permutation_matches_dense_permutation():
     pads = batch["attention_mask"].left_pads()
     row_of = lambda b, s: offs[b] + s - pads[b]
     S0 = C * bl
-    plan = E.StaticDenoiser._hoist_plan(lay, S0, lay.L, row_of, batch["denoise_image_sizes"], batch["time_emb_inx"])
+    plan = SP._hoist_plan(lay, S0, lay.L, row_of, batch["denoise_image_sizes"], batch["time_emb_inx"])
     assert plan is not None and plan["nf"] == 2 * G and plan["ntok"] == N and plan["S"] == 128
     perm = np.array(plan["perm"])
     assert sorted(perm[perm >= 0].tolist()) == list(range(lay.L))          # a permutation (plus gap rows)
@@ -180,7 +181,7 @@ def test_hoist_plan_permutation_matches_dense_permutation():
     assert plan["segments"] == ((0, S, S + G * N), (0, S + G * N, S + 2 * G * N))
     # a layout whose tail is not whole noisy frames is refused
     bad = {0: batch["denoise_image_sizes"][0][:-1], 1: batch["denoise_image_sizes"][1]}
-    assert E.StaticDenoiser._hoist_plan(lay, S0, lay.L, row_of, bad, batch["time_emb_inx"]) is None
+    assert SP._hoist_plan(lay, S0, lay.L, row_of, bad, batch["time_emb_inx"]) is None
 
 
 def test_left_pads_are_not_inferred_from_rows_that_merely_see_everything():
@@ -206,14 +207,14 @@ def _clip_pass_layout(C=2, G=3, N=16, T=4):
     pads = batch["attention_mask"].left_pads()
     row_of = lambda b, s: offs[b] + s - pads[b]
     S0 = C * bl
-    plan = E.StaticDenoiser._hoist_plan(lay, S0, lay.L, row_of, batch["denoise_image_sizes"], batch["time_emb_inx"])
+    plan = SP._hoist_plan(lay, S0, lay.L, row_of, batch["denoise_image_sizes"], batch["time_emb_inx"])
     hoisted = lay.permute(np.array(plan["perm"]))
     nf = plan["nf"]
     Sc = S0 + nf
-    idx = np.concatenate([np.arange(Sc), np.tile(np.arange(Sc, Sc + nf), T)])
+    idx, sub_tail = SP.clip_pass_rows(S0, nf, T)
     lp = hoisted.permute(idx)
     sub = lp.sub.copy()
-    sub[0, Sc:] = 1 + np.repeat(np.arange(T), nf)
+    sub[0, Sc:] = sub_tail
     return hoisted, lp.with_subgroups(sub), S0, nf, T
 
 

@@ -16,82 +16,15 @@ from __future__ import annotations
 import os
 import weakref
 from types import SimpleNamespace
-from typing import Dict, List, Optional
+from typing import Optional
 
 import torch
 
 from . import ops
 from .layout import TokenLayout
 from .ops import BF16, VgptError
-
-
-def _rows(sizes: Dict[int, list], row_of, span: bool):
-    out = []
-    for b in sizes.keys():
-        for item in sizes[b]:
-            out.append(row_of(b, item[0] if span else item))
-    return out
-
-
-def count_left_pads(attention_mask) -> List[int]:
-    """Left-pad length of every row, read off the mask itself: pad rows are the leading all-ones rows
-    (LVM/processor.py:726-727); a real first token only sees itself."""
-    if isinstance(attention_mask, TokenLayout):
-        return attention_mask.left_pads()
-    B, L, _ = attention_mask.shape
-    if L <= 1:
-        return [0] * B
-    mb = attention_mask.to(torch.bool)
-    lead = [int(v) for v in torch.cumprod(mb.all(-1).to(torch.int64), dim=1).sum(1).tolist()]
-    # leading all-ones rows are padding only in the collator's pattern, where the first real row does not see the pad
-    # columns (LVM/processor.py:722-727).  A mask whose first rows simply see everything (a caller's full bidirectional
-    # mask) has no padding: packing it would drop real tokens.
-    for b, n in enumerate(lead):
-        if n and (n >= L or bool(mb[b, n, :n].any())):
-            lead[b] = 0
-    return lead
-
-
-def pack_left_padded(input_ids, position_ids, attention_mask, pads: List[int]):
-    """Drop the left-pad tokens of every batch row and lay the real tokens of all rows out as ONE
-    sequence with a block-diagonal mask (row b's real-token sub-mask on the diagonal, everything
-    between different rows masked).  Pad rows never influence real rows (pad columns are masked,
-    LVM/processor.py:722-727) and the model only reads real positions, so the outputs are unchanged;
-    the attention kernel skips the off-diagonal tiles through its tile summary.
-    Returns (ids (1,M), positions (1,M), mask (1,M,M) bool, offsets, pads)."""
-    B, L = input_ids.shape
-    lens = [L - p for p in pads]
-    offsets = [0]
-    for n in lens[:-1]:
-        offsets.append(offsets[-1] + n)
-    M = sum(lens)
-    ids = torch.cat([input_ids[b, pads[b]:] for b in range(B)]).view(1, M)
-    pos = torch.cat([position_ids[b, pads[b]:] for b in range(B)]).view(1, M)
-    if isinstance(attention_mask, TokenLayout):   # tokens keep their sequence id: block-diagonal by construction
-        return ids.contiguous(), pos.contiguous(), attention_mask.pack(pads)[0], offsets
-    mask = torch.zeros(1, M, M, dtype=torch.bool, device=attention_mask.device)
-    for b in range(B):
-        o, n, p = offsets[b], lens[b], pads[b]
-        mask[0, o:o + n, o:o + n] = attention_mask[b, p:, p:].to(torch.bool)
-    return ids.contiguous(), pos.contiguous(), mask, offsets
-
-
-def sp_shares(M: int, P: int):
-    """Contiguous shares [(begin, end)] of M rows over P ranks, in rank order, and the cut granularity: shares of a
-    multiple of 256 rows (full GEMM tiles) where that keeps the largest share within 1/8 of an even split and leaves every
-    rank rows, else of 64 or 16 rows, else an even split (ragged shares differ by at most one row)."""
-    if M < P:
-        raise VgptError(f"sequence parallelism: {M} rows cannot be shared by {P} ranks")
-    even = -(-M // P)
-    for g in (256, 64, 16):
-        c = -(-even // g) * g
-        if c <= even + even // 8 and (P - 1) * c < M:
-            return [(min(r * c, M), min((r + 1) * c, M)) for r in range(P)], g
-    q, rem = divmod(M, P)
-    b = [0]
-    for r in range(P):
-        b.append(b[-1] + q + (r < rem))
-    return list(zip(b[:-1], b[1:])), 1
+from .step_plan import (_hoist_plan, _rows, clip_pass_rows, count_left_pads, pack_left_padded,  # noqa: F401 (re-exported)
+                        plan_step_rows, sp_final_layer_owners, sp_shares)
 
 
 _FOLDED = weakref.WeakKeyDictionary()   # model -> (key, qkv weights, gate_up weights) with the RMSNorm gains folded in
@@ -136,6 +69,8 @@ def folded_weights(model):
 
 
 class StaticDenoiser:
+    _hoist_plan = staticmethod(_hoist_plan)   # its home before step_plan.py; callers of the old name keep working
+
     def __init__(self, model, input_ids, position_ids, attention_mask, input_img_latents, input_image_sizes,
                  denoise_image_sizes, time_emb_inx, n_frames: int, latent_hw, use_img_cfg: bool, img_cfg_scale: float,
                  prediction_type: str = "v", sigma: Optional[torch.Tensor] = None, pack_padding: bool = True,
@@ -188,96 +123,22 @@ class StaticDenoiser:
         self.cfg = cfg
         dev = input_ids.device
         self.dev = dev
-        B, L = input_ids.shape
-        row_of = lambda b, s: b * L + s
-        self.packed = False
-        seq_bounds = None   # packed layout: row range of every original batch row, for the attention plan
-        pads = count_left_pads(attention_mask) if pack_padding and not isinstance(attention_mask, ops.PackedMask) else []
-        if any(pads):
-            input_ids, position_ids, attention_mask, offs = pack_left_padded(input_ids, position_ids, attention_mask, pads)
-            row_of = lambda b, s: offs[b] + s - pads[b]
-            seq_bounds = [(offs[b], offs[b] + (L - pads[b])) for b in range(B)]
-            B, L = input_ids.shape
-            self.packed = True
-        # ---- condition-prefix reuse: rows before the first <|diffusion|> token never see a
-        #      noisy / time token (LVM/processor.py:682-731), so their activations are identical at every denoise
-        #      step; the reference recomputes them 50x (LVM/scheduler.py:174).  They are computed ONCE (prefill),
-        #      their per-layer K/V stay in a full-length qkv buffer, and a step only runs the remaining rows. ----
-        self.S = 0          # static prefix length in the (padded) layout == first computed row, multiple of 128
-        self.S0 = 0         # rows the prefill computes (== S without hoisting: the alignment rows ride along)
-        self.hoist = None   # special-row hoisting (below): dict(nf, steps tensors ...) when active
-        hoist_seg = None
-        if reuse_condition_prefix and B == 1 and not isinstance(attention_mask, ops.PackedMask):
-            t_first = min(row_of(b, t) for b in time_emb_inx.keys() for t in time_emb_inx[b]) - 1
-            is_layout = isinstance(attention_mask, TokenLayout)
-            m2 = None if is_layout else attention_mask[0].to(torch.bool)
-            static = t_first >= 128 and (attention_mask.prefix_is_static(t_first) if is_layout
-                                         else not bool(m2[:t_first, t_first:].any()))
-            plan = None
-            if static and hoist_special_rows and is_layout:
-                plan = self._hoist_plan(attention_mask, t_first, L, row_of, denoise_image_sizes, time_emb_inx)
-            if plan is not None:
-                # ---- special-row hoisting: the `<|diffusion|>` row of a noisy frame sees only `<|diffusion|>` columns
-                #      and the condition prefix, its time row only those and the time columns — never an image column
-                #      (LVM/processor.py:682-731) — so the first is step-invariant and the second a function of the step
-                #      index alone.  Both leave the per-step row set: the sequence is re-ordered to
-                #      [prefix | diffusion rows | time rows | gap | image rows], the image rows (n_frames x N: whole
-                #      GEMM / attention tiles) are all a step computes, and the time rows' q/k/v of EVERY step come
-                #      from the per-clip pass (_clip_pass) and are dropped in by vgpt_sampler_copy_step_rows. ----
-                perm, S, inv = plan["perm"], plan["S"], plan["inv"]
-                pt = torch.tensor([p_ if p_ >= 0 else 0 for p_ in perm], dtype=torch.int64, device=input_ids.device)
-                gapm = torch.tensor([p_ < 0 for p_ in perm], dtype=torch.bool, device=input_ids.device)
-                input_ids = torch.where(gapm, input_ids[0, 0], input_ids[0, pt]).view(1, -1)
-                position_ids = torch.where(gapm, torch.zeros_like(position_ids[0, pt]), position_ids[0, pt]).view(1, -1)
-                attention_mask = attention_mask.permute(perm)
-                prev = row_of
-                row_of = lambda b, s, prev=prev, inv=inv: inv[prev(b, s)]
-                L = len(perm)
-                self.S, self.S0 = S, t_first
-                self.hoist = plan
-                hoist_seg = plan["segments"]
-                seq_bounds = None
-            elif static:
-                S0 = t_first
-                S = (S0 + 127) // 128 * 128
-                npad = S - S0
-                dev0 = input_ids.device
-                pad_ids = torch.full((1, npad), int(input_ids[0, 0]), dtype=input_ids.dtype, device=dev0)
-                input_ids = torch.cat([input_ids[:, :S0], pad_ids, input_ids[:, S0:]], dim=1)
-                position_ids = torch.cat([position_ids[:, :S0], torch.zeros(1, npad, dtype=position_ids.dtype, device=dev0),
-                                          position_ids[:, S0:]], dim=1)
-                L2 = L + npad
-                if is_layout:
-                    attention_mask = attention_mask.insert_gap(S0, npad)
-                else:
-                    mask2 = torch.zeros(1, L2, L2, dtype=torch.bool, device=m2.device)
-                    mask2[0, :S0, :S0] = m2[:S0, :S0]
-                    mask2[0, S:, :S0] = m2[S0:, :S0]
-                    mask2[0, S:, S:] = m2[S0:, S0:]
-                    attention_mask = mask2
-                prev = row_of
-                row_of = lambda b, s, prev=prev, S0=S0, npad=npad: (lambda r: r if r < S0 else r + npad)(prev(b, s))
-                L = L2
-                self.S = self.S0 = S
-                if seq_bounds is not None:
-                    sh = lambda r_: r_ if r_ < S0 else r_ + npad
-                    seq_bounds = [(sh(a_), sh(e_ - 1) + 1) for a_, e_ in seq_bounds]
-        H, I = cfg.hidden_size, cfg.intermediate_size
-        self.B, self.L, self.H = B, L, H
-        # query-row segments of the attention plan: cut where two packed sequences meet (their key sets differ) so
-        # that no work item of the kernel straddles them; `seg_live` covers the rows computed at every step
-        self.seg_all = self.seg_live = None
-        if seq_bounds is not None and B == 1:
-            cuts = sorted({0, L, *[a_ for a_, _ in seq_bounds]})
-            self.seg_all = tuple((0, a_, e_) for a_, e_ in zip(cuts[:-1], cuts[1:]) if e_ > a_)
-            if self.S:
-                cl = sorted({self.S, L, *[a_ for a_, _ in seq_bounds if a_ > self.S]})
-                self.seg_live = tuple((0, a_, e_) for a_, e_ in zip(cl[:-1], cl[1:]) if e_ > a_)
-        if hoist_seg is not None:
-            self.seg_live = hoist_seg
+
+        # ---- the row plan (step_plan.py): left pads dropped and the batch packed into one sequence, the step-invariant
+        #      condition prefix found and, behind it, the special rows hoisted or an alignment gap inserted ----
+        plan = plan_step_rows(input_ids, position_ids, attention_mask, input_image_sizes, denoise_image_sizes, time_emb_inx,
+                              pack_padding=pack_padding, reuse_condition_prefix=reuse_condition_prefix,
+                              hoist_special_rows=hoist_special_rows)
+        B, L, S = plan.B, plan.L, plan.S
+        self.B, self.L, self.H = B, L, cfg.hidden_size
+        self.packed = plan.packed
+        self.S = S              # static prefix length in the (padded) layout == first computed row, multiple of 128
+        self.S0 = plan.S0       # rows the prefill computes (== S without hoisting: the alignment rows ride along)
+        self.hoist = plan.hoist  # special-row hoisting: step_plan._hoist_plan's dict when active
+        self.Ma = B * L - S     # rows computed per step
+        self.seg_all, self.seg_live = plan.seg_all, plan.seg_live
         self.nf = n_frames
         self.h, self.w = latent_hw
-        C = model.in_channels
         self.use_cfg = bool(use_img_cfg)
         self.cfg_scale = float(img_cfg_scale)
         if prediction_type not in ("v", "x1"):
@@ -285,13 +146,15 @@ class StaticDenoiser:
         self.pred_type = ops.PRED_X1 if prediction_type == "x1" else ops.PRED_V
         if self.use_cfg and n_frames % 2:
             raise VgptError("CFG needs an even number of latent frames")
+        if len(plan.x_rows) != n_frames or len(plan.t_rows) != n_frames:
+            raise AssertionError("denoise_image_sizes / time_emb_inx disagree with the number of latents")
 
         # static inputs
-        self.input_ids = input_ids.contiguous()
-        self.pm = ops.as_packed_mask(attention_mask, dev)
-        self.layout = attention_mask if isinstance(attention_mask, TokenLayout) else None
-        self.position_ids = position_ids
-        self.rope = model.llm.rope_tables(position_ids)
+        self.input_ids = plan.input_ids.contiguous()
+        self.pm = ops.as_packed_mask(plan.attention_mask, dev)
+        self.layout = plan.attention_mask if isinstance(plan.attention_mask, TokenLayout) else None
+        self.position_ids = plan.position_ids
+        self.rope = model.llm.rope_tables(plan.position_ids)
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
         self.cond = None
         if input_img_latents is not None and len(input_img_latents) > 0:
@@ -299,55 +162,83 @@ class StaticDenoiser:
             if len(shapes) != 1:
                 raise VgptError("StaticDenoiser needs condition frames of one resolution")
             self.cond = torch.cat([t.to(BF16) for t in input_img_latents], dim=0).contiguous()
-            rows = _rows(input_image_sizes, row_of, True)
-            if len(rows) != self.cond.shape[0]:
+            if len(plan.cond_rows) != self.cond.shape[0]:
                 raise AssertionError("input_image_sizes and input_img_latents disagree")
-            self.cond_rows = i32(rows)
-        x_rows = _rows(denoise_image_sizes, row_of, True)
-        t_rows = _rows(time_emb_inx, row_of, False)
-        if len(x_rows) != n_frames or len(t_rows) != n_frames:
-            raise AssertionError("denoise_image_sizes / time_emb_inx disagree with the number of latents")
-        self.x_rows, self.t_rows = i32(x_rows), i32(t_rows)
-        S = self.S
-        self.Ma = B * L - S   # rows computed per step
+            self.cond_rows = i32(plan.cond_rows)
+        self.x_rows, self.t_rows = i32(plan.x_rows), i32(plan.t_rows)
+        # ---- the live rows [S, B L): what a step computes, as views every step method reads (`_a`).  Without a reused
+        #      prefix they ARE the whole sequence; this is the one place that tells the two cases apart ----
         if S:
-            self.x_rows_a = i32([r - S for r in x_rows])
-            self.t_rows_a = None if self.hoist else i32([r - S for r in t_rows])
+            self.x_rows_a = i32([r - S for r in plan.x_rows])
+            self.t_rows_a = None if self.hoist else i32([r - S for r in plan.t_rows])   # hoisted: no time row is live
             self.ids_a = self.input_ids[:, S:].contiguous()
             self.rope_a = (self.rope[0][S:].contiguous(), self.rope[1][S:].contiguous())
+            self.seg_a = self.seg_live
+        else:
+            self.x_rows_a, self.t_rows_a, self.ids_a, self.rope_a = self.x_rows, self.t_rows, self.input_ids, self.rope
+            self.seg_a = self.seg_all
 
-        # per-step state
-        M = B * L
-        e = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)
-        self.z = e(n_frames, C * self.h * self.w, dt=torch.float32)
-        self.z_model = e(n_frames, C, self.h, self.w)
-        self.pred = e(n_frames, C, self.h, self.w)
+        self.heads = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        self._alloc_state(sigma)
+        self._alloc_workspaces()
+        self._set_projection_mode(fuse_norms)
+        self._alloc_step_buffers()
+        self._initial_passes()
+
+    # ---- allocation, once per engine ------------------------------------------------------------------------------------
+    def _alloc_state(self, sigma):
+        """The sampler state: latents, prediction, velocity history, timesteps, step counter, sigma table."""
+        nf, C = self.nf, self.model.in_channels
+        e = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=self.dev)
+        self.z = e(nf, C * self.h * self.w, dt=torch.float32)
+        self.z_model = e(nf, C, self.h, self.w)
+        self.pred = e(nf, C, self.h, self.w)
         # ab2 / heun: the guided velocity of the step, one CFG half.  Never cleared between clips: step 0 writes it before
         # anything reads it (ab2 reads from step 1 on, the Heun corrector after its own predictor)
-        self.v_hist = None if self.solver == ops.SOLVER_EULER else e(n_frames // (2 if self.use_cfg else 1),
-                                                                     C * self.h * self.w, dt=torch.float32)
-        self.ts = e(n_frames, dt=torch.float32)
-        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.v_hist = None if self.solver == ops.SOLVER_EULER else e(nf // (2 if self.use_cfg else 1), C * self.h * self.w,
+                                                                     dt=torch.float32)
+        self.ts = e(nf, dt=torch.float32)
+        self.step = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.sigma = None
         if sigma is not None:
-            self.sigma = sigma.to(dev, torch.float32).contiguous()
+            self.sigma = sigma.to(self.dev, torch.float32).contiguous()
             self.num_steps = self.sigma.numel() - 1
-        # workspaces
-        self.heads = nq, nk, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+
+    def _alloc_step_buffers(self):
+        """The small buffers of a step around the decoder layers (time token, t_embedder, adaLN modulation), and the slots
+        the per-clip passes and the capture fill."""
+        nf, H = self.nf, self.H
+        e = lambda *s: torch.empty(*s, dtype=BF16, device=self.dev)
+        self.temb_sin = e(nf, 256)
+        self.tt_h = e(nf, H)
+        self.te_h = e(nf, H)
+        self.temb = e(nf, H)
+        self.mod = e(nf, 2 * H)
+        self.graph = self.graph_last = None
+        self.time_qkv = None   # hoisting: (steps, layers, n_frames, 3H) q/k/v rows of the time tokens of every step
+        self.mod_all = None    # (steps, 1, n_frames, 2H) adaLN shift / scale of the final layer for every step (_mod_pass)
+        self.steps_taken = 0
+
+    def _alloc_workspaces(self):
+        """Activations and q/k/v of the per-step forward: this rank's share of the live rows (sharded), the live rows behind
+        a cached prefix with one full-length q/k/v buffer per layer, or every row with one q/k/v buffer."""
+        cfg, dev, B, L, H, Ma = self.cfg, self.dev, self.B, self.L, self.H, self.Ma
+        nq, nk, hd = self.heads
+        I = cfg.intermediate_size
+        e = lambda *s: torch.empty(*s, dtype=BF16, device=dev)
         if self.sp is not None:
             if B != 1:
                 raise VgptError("StaticDenoiser: sequence_parallel needs one packed sequence (a batch of one, or left-padded "
                                 "rows with pack_padding=True)")
             self._sp_plan()
-        elif S:
-            Ma = self.Ma
+        elif self.S:
             self.hid, self.nrm, self.ctx, self.act = e(1, Ma, H), e(1, Ma, H), e(1, Ma, nq * hd), e(1, Ma, I)
             self.qkv_full = torch.zeros(cfg.num_hidden_layers, L, (nq + 2 * nk) * hd, dtype=BF16, device=dev)
             if self.attn_fp8:
                 # one fp8 workspace per layer (51 MB at cfg-2): prefill() quantises the step-invariant rows once, a step
                 # only the rows from the first one it writes on (the time rows of a hoisted layout sit below S)
                 self.fp8_ws = [ops.attention_fp8_workspace_hd(1, L, nq, nk, hd, dev) for _ in range(cfg.num_hidden_layers)]
-                first = (self.S0 + self.hoist["nf"]) if self.hoist else S
+                first = (self.S0 + self.hoist["nf"]) if self.hoist else self.S
                 self.fp8_from = first // 64 * 64
         else:
             self.hid = e(B, L, H)
@@ -355,6 +246,13 @@ class StaticDenoiser:
             self.qkv = e(B, L, (nq + 2 * nk) * hd)
             self.ctx = e(B, L, nq * hd)
             self.act = e(B, L, I)
+
+    def _set_projection_mode(self, fuse_norms):
+        """How the per-step forward runs a layer's projections: `mx8` (MX-fp8 records), `fuse` (both RMSNorms folded into
+        the bf16 GEMMs around them), or neither (separate RMSNorm kernels)."""
+        model, dev, H = self.model, self.dev, self.H
+        nq, nk, hd = self.heads
+        I = self.cfg.intermediate_size
         self.fuse = None
         if fuse_norms is None:
             fuse_norms = os.environ.get("VGPT_FUSE_NORMS", "1") != "0"
@@ -362,7 +260,7 @@ class StaticDenoiser:
         if self.lin_fp8:
             # the fp8 step folds both RMSNorms itself (row quantiser -> rstd, gain in the quantised weight): no folded bf16
             # copies.  Records at stable addresses (a captured graph reads them), weights refilled by every per_clip_setup()
-            Ms = self.Ma if S else B * L
+            Ms = self.Ma
             W3 = (nq + 2 * nk) * hd
             mk = lambda rows, K: ops.Mx8Tensor(rows, K, dev)
             self.mx8 = {"a_hid": mk(Ms, H), "a_ctx": mk(Ms, nq * hd), "a_act": mk(Ms, I),
@@ -371,7 +269,7 @@ class StaticDenoiser:
                               for _ in model.llm.layers]}
             self.quantize_weights()
         elif fuse_norms:
-            Ms = self.sp["m"] if self.sp else (self.Ma if S else B * L)
+            Ms = self.sp["m"] if self.sp else self.Ma
             wa, wb = ops.norm_workspace_bytes(Ms, H, nq * hd), ops.norm_workspace_bytes(Ms, H, I)
             if wa > 0 and wb > 0:
                 wq, wgu = folded_weights(model)
@@ -379,18 +277,12 @@ class StaticDenoiser:
                 self.fuse = {"rstd_in": torch.empty(Ms, dtype=torch.float32, device=dev),
                              "rstd_post": torch.empty(Ms, dtype=torch.float32, device=dev),
                              "ws": ops.norm_workspace(max(wa, wb), dev), "wq": wq, "wgu": wgu}
-        self.temb_sin = e(n_frames, 256)
-        self.tt_h = e(n_frames, H)
-        self.te_h = e(n_frames, H)
-        self.temb = e(n_frames, H)
-        self.mod = e(n_frames, 2 * H)
-        self.graph = self.graph_last = None
-        self.time_qkv = None   # hoisting: (steps, layers, n_frames, 3H) q/k/v rows of the time tokens of every step
-        self.mod_all = None    # (steps, 1, n_frames, 2H) adaLN shift / scale of the final layer for every step (_mod_pass)
-        self.steps_taken = 0
+
+    def _initial_passes(self):
+        """The per-clip passes of the first clip (per_clip_setup repeats them for the next one)."""
         if self.sigma is not None:
             self._mod_pass()
-        if S:
+        if self.S:
             if self.hoist and self.sigma is not None:
                 self._clip_pass()
             else:
@@ -589,52 +481,17 @@ class StaticDenoiser:
         self.mod_all.copy_(mod.view(T, 1, 1, 2 * H).expand(*shape))
 
     # ---- special-row hoisting ------------------------------------------------------------------------------------
-    @staticmethod
-    def _hoist_plan(layout: TokenLayout, S0: int, L: int, row_of, denoise_image_sizes, time_emb_inx):
-        """Re-ordering [prefix | diffusion rows | time rows | gap | image rows] of a packed next-clip sequence, or None
-        when the rows behind the prefix are not exactly whole noisy frames (then only the prefix is reused)."""
-        from .layout import NOISY
-        x_old = _rows(denoise_image_sizes, row_of, True)
-        t_old = _rows(time_emb_inx, row_of, False)
-        ntoks = {it[1] - it[0] for b in denoise_image_sizes.keys() for it in denoise_image_sizes[b]}
-        nf = len(x_old)
-        if nf == 0 or len(t_old) != nf or len(ntoks) != 1:
-            return None
-        ntok = ntoks.pop()
-        if any(t != x - 1 for t, x in zip(t_old, x_old)):
-            return None
-        d_old = [t - 1 for t in t_old]
-        rows = sorted(d_old + t_old + [x + j for x in x_old for j in range(ntok)])
-        if rows != list(range(S0, L)) or not bool((layout.kind[0, S0:] == NOISY).all()):
-            return None
-        # the special rows must really be the offset-0 / offset-1 tokens of their frames (what makes them image-blind)
-        if not (bool((layout.oc[0, d_old] == 0).all()) and bool((layout.oc[0, t_old] == 1).all())
-                and bool((layout.oc[0, [x + j for x in x_old for j in range(ntok)]] == 2).all())):
-            return None
-        S = (S0 + 2 * nf + 127) // 128 * 128
-        perm = list(range(S0)) + d_old + t_old + [-1] * (S - S0 - 2 * nf) + [x + j for x in x_old for j in range(ntok)]
-        inv = {o: i for i, o in enumerate(perm) if o >= 0}
-        # image rows of one sequence form one segment of the attention plan
-        seqs = [int(layout.seq[0, x]) for x in x_old]
-        segs, f0 = [], 0
-        for f in range(1, nf + 1):
-            if f == nf or seqs[f] != seqs[f0]:
-                segs.append((0, S + f0 * ntok, S + f * ntok))
-                f0 = f
-        return dict(perm=perm, inv=inv, S=S, nf=nf, ntok=ntok, segments=tuple(segs))
-
     def _clip_layout(self):
         """Mask and row counts of the per-clip pass of a hoisted layout (_clip_pass): pm, Sc (the rows the sampler steps read
         from the cache: prefix + `<|diffusion|>` rows), Lp (all rows of the pass).  The time rows of step s carry sub-group
         s + 1 (layout.TokenLayout): they see the prefix, their clip's `<|diffusion|>` columns (sub-group 0) and the time
         columns of their own step only."""
-        import numpy as np
         nf, T = self.hoist["nf"], self.num_steps
         Sc = self.S0 + nf
-        idx = np.concatenate([np.arange(Sc), np.tile(np.arange(Sc, Sc + nf), T)])
+        idx, sub_tail = clip_pass_rows(self.S0, nf, T)
         lp = self.layout.permute(idx)
         sub = lp.sub.copy()
-        sub[0, Sc:] = 1 + np.repeat(np.arange(T), nf)
+        sub[0, Sc:] = sub_tail
         return lp.with_subgroups(sub).packed_mask(self.dev), Sc, Sc + T * nf
 
     def _clip_pass(self):
@@ -709,7 +566,7 @@ class StaticDenoiser:
             raise VgptError(f"StaticDenoiser: sequence_parallel over {P} ranks needs num_attention_heads ({nq}) and "
                             f"num_key_value_heads ({nk}) divisible by {P}")
         S, L = self.S, self.L
-        Ml = L - S                                            # live rows of a step
+        Ml = self.Ma                                          # live rows of a step
         shares, cut = sp_shares(Ml, P)
         a, b = shares[r]
         m = b - a
@@ -725,14 +582,7 @@ class StaticDenoiser:
         self.qkv_full = torch.zeros(cfg.num_hidden_layers if S else 1, L, Wl, dtype=BF16, device=dev)
         self.sp_bufs = self._sp_buffers(Ml, m)
         # the final layer: frames with a row in this share, and for every element of pred the rank that computed it
-        x_rows = [int(v) for v in (self.x_rows_a if S else self.x_rows).tolist()]
-        ntok = (self.h // 2) * (self.w // 2)
-        mine = [f for f, x0 in enumerate(x_rows) if x0 < b and x0 + ntok > a]
-        self.sp_frames = (mine[0], mine[-1] + 1) if mine else (0, 0)
-        bounds = torch.tensor([e_ for _, e_ in shares], dtype=torch.int64)
-        tok = (torch.arange(self.h)[:, None] // 2) * (self.w // 2) + torch.arange(self.w)[None, :] // 2
-        rows = torch.tensor(x_rows, dtype=torch.int64)[:, None, None] + tok[None]          # (nf, h, w) live row
-        owner = torch.bucketize(rows, bounds, right=True)                                     # share index of the row
+        self.sp_frames, owner = sp_final_layer_owners(self.x_rows_a.tolist(), self.h, self.w, shares, r)
         C = self.pred.shape[1]
         self.sp_owner = owner[:, None].expand(-1, C, -1, -1).reshape(1, -1).to(dev)
         self.pred_loc = torch.zeros_like(self.pred)
@@ -782,9 +632,8 @@ class StaticDenoiser:
         m, H, S = self.model, self.H, self.S
         hid = self.hid if self.sp is None else self.hid_all
         seq2d = hid.view(-1, H)
-        x_rows, t_rows = (self.x_rows_a, self.t_rows_a) if S else (self.x_rows, self.t_rows)
         if not self.hoist:   # a hoisted step's live rows are image rows only: the patch embedding below writes every one
-            ops.embed_gather(self.ids_a if S else self.input_ids, m.llm.embed_tokens.weight, out=hid)
+            ops.embed_gather(self.ids_a, m.llm.embed_tokens.weight, out=hid)
         if not S:
             self._embed_cond(seq2d)
         if not (from_tables and self.hoist):
@@ -796,8 +645,8 @@ class StaticDenoiser:
         else:
             tt = m.time_token.mlp
             ops.linear_small(self.temb_sin, tt[0].weight, tt[0].bias, post_act=ops.ACT_SILU, out=self.tt_h)
-            ops.linear_small(self.tt_h, tt[2].weight, tt[2].bias, out=seq2d, out_row=t_rows, ldo=H)
-        ops.patch_embed(self.z_model, m.x_embedder.proj.weight, m.x_embedder.proj.bias, m.pos_embed[0], x_rows, seq2d,
+            ops.linear_small(self.tt_h, tt[2].weight, tt[2].bias, out=seq2d, out_row=self.t_rows_a, ldo=H)
+        ops.patch_embed(self.z_model, m.x_embedder.proj.weight, m.x_embedder.proj.bias, m.pos_embed[0], self.x_rows_a, seq2d,
                         m.pos_embed_max_size)
 
     def _step_tail(self, from_tables: bool):
@@ -805,7 +654,6 @@ class StaticDenoiser:
         + unpatchify into `pred`.  Sharded: each rank runs the final layer on the frames it owns rows of, and one all-gather
         (owner-selected per element) leaves the full `pred` on every rank."""
         m, H, sp = self.model, self.H, self.sp
-        x_rows = self.x_rows_a if self.S else self.x_rows
         if sp is None:
             (f0, f1), nrm_all, nrm, pred = (0, self.nf), self.nrm, self.nrm, self.pred
         else:
@@ -824,7 +672,7 @@ class StaticDenoiser:
             if self.nf > 1:
                 self.mod[1:].copy_(self.mod[:1].expand(self.nf - 1, -1))
         if f1 > f0:
-            ops.final_layer(nrm_all.view(-1, H), x_rows[f0:f1], self.mod[f0:f1], m.final_layer.linear.weight,
+            ops.final_layer(nrm_all.view(-1, H), self.x_rows_a[f0:f1], self.mod[f0:f1], m.final_layer.linear.weight,
                             m.final_layer.linear.bias, pred[f0:f1])
         if sp is not None:
             from . import sequence_parallel as SPM
@@ -837,12 +685,13 @@ class StaticDenoiser:
         from_tables = from_tables and self.mod_all is not None
         self._step_head(from_tables)
         nq, nk, hd = self.heads
-        S, pm, ctx, rows = self.S, self.pm, self.ctx, self.attn_item_rows
-        rope = self.rope_a if S else self.rope
+        S, pm, ctx, rows, seg, rope = self.S, self.pm, self.ctx, self.attn_item_rows, self.seg_a, self.rope_a
         if self.sp is not None:
             rope = tuple(t_[self.sp["a"]:self.sp["b"]] for t_ in rope)
-            qkv_dst, attention = self._sp_attention(self.sp_bufs, self.sp["shares"], lambda li: self.qkv_full[li if S else 0], S,
-                                                    pm, self.seg_live if S else self.seg_all, ctx, item_rows=rows)
+            # (one fused buffer serves every layer when no prefix is cached: _sp_plan)
+            qkv_dst, attention = self._sp_attention(self.sp_bufs, self.sp["shares"],
+                                                    lambda li: self.qkv_full[li % len(self.qkv_full)], S, pm, seg, ctx,
+                                                    item_rows=rows)
         elif S:
             qkv_dst = lambda li: self.qkv_full[li][S:]       # this step's q/k/v rows, behind the cached prefix
 
@@ -850,18 +699,18 @@ class StaticDenoiser:
                 full = self.qkv_full[li].view(1, self.L, -1)
                 if self.attn_fp8:
                     # the prefix rows were quantised once by prefill(); a step re-quantises from the first row it writes
-                    ops.attention_qkv_fp8_hd(full, pm, nq, nk, hd, out=ctx, q_start=S, segments=self.seg_live,
+                    ops.attention_qkv_fp8_hd(full, pm, nq, nk, hd, out=ctx, q_start=S, segments=seg,
                                           workspace=self.fp8_ws[li], quant_from=self.fp8_from)
                 else:
-                    ops.attention_qkv_range(full, pm, nq, nk, hd, S, ctx, segments=self.seg_live, item_rows=rows)
+                    ops.attention_qkv_range(full, pm, nq, nk, hd, S, ctx, segments=seg, item_rows=rows)
         else:
             qkv_dst = lambda li: self.qkv
 
             def attention(li):
                 if self.attn_fp8:
-                    ops.attention_qkv_fp8_hd(self.qkv, pm, nq, nk, hd, out=ctx, segments=self.seg_all)
-                elif self.seg_all is not None:
-                    ops.attention_qkv_range(self.qkv, pm, nq, nk, hd, 0, ctx, segments=self.seg_all, item_rows=rows)
+                    ops.attention_qkv_fp8_hd(self.qkv, pm, nq, nk, hd, out=ctx, segments=seg)
+                elif seg is not None:
+                    ops.attention_qkv_range(self.qkv, pm, nq, nk, hd, 0, ctx, segments=seg, item_rows=rows)
                 else:
                     ops.attention_qkv(self.qkv, pm, nq, nk, hd, out=ctx)
         self._layers(self.hid, self.nrm, ctx, self.act, rope, qkv_dst, attention, fz=self.fuse, mx=self.mx8)

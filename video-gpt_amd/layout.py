@@ -127,7 +127,7 @@ class TokenLayout:
         return [int(v) for v in lead]
 
     def pack(self, pads: Optional[List[int]] = None):
-        """Drop every row's left pads and lay all rows out as ONE sequence (engine.pack_left_padded): tokens keep
+        """Drop every row's left pads and lay all rows out as ONE sequence (step_plan.pack_left_padded): tokens keep
         their sequence id, so the mask of the packed row is block-diagonal by construction.
         Returns (layout with B == 1, offsets of the rows in the packed sequence)."""
         pads = self.left_pads() if pads is None else pads
