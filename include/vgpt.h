@@ -442,6 +442,18 @@ int vgpt_euler_cfg_update(float* z, void* z_model, const void* pred, const float
 int vgpt_sampler_update(float* z, void* z_model, const void* pred, float* v_hist, const float* sigma,
                         const int32_t* step, int n_steps, int n_frames, int64_t elems, int pred_type, int use_cfg,
                         float cfg_scale, int solver, int stage, void* stream);
+/* vgpt_sampler_update with image CFG under a per-step guidance scale: cfg_table (n_steps fp32
+ * entries, device memory) in place of cfg_scale, and no use_cfg -- this entry point is CFG by definition (n_frames even:
+ * first half conditional, second half unconditional).  The scale of a launch is cfg_table[i] with i the index the launch
+ * reads sigma at: *step, and *step - 1 for the Heun corrector, so both model calls of a Heun step use that step's scale.
+ * An entry that is EXACTLY 1.0f marks an unguided step: v = v_c, the unconditional half of `pred` is not loaded (a caller
+ * may leave it uncomputed), both halves of z / z_model still move by v in the roundings of the guided kernels, and
+ * v_hist keeps v.  With one value s != 1 in every entry each launch gives the bits of vgpt_sampler_update(..., use_cfg = 1,
+ * cfg_scale = s, ...).  A launch with i outside the table is a no-op.  VGPT_ERR_INVALID as vgpt_sampler_update, and for a
+ * null cfg_table and an odd n_frames. */
+int vgpt_sampler_update_sched(float* z, void* z_model, const void* pred, float* v_hist, const float* sigma,
+                              const float* cfg_table, const int32_t* step, int n_steps, int n_frames, int64_t elems,
+                              int pred_type, int solver, int stage, void* stream);
 /* *step += 1 */
 int vgpt_sampler_advance(int32_t* step, void* stream);
 /* dst[l][0:slab_bytes] = src[*step][l][0:slab_bytes] for l < n_layers (step clamped to [0, n_steps)); all sizes and

@@ -347,6 +347,81 @@ __global__ __launch_bounds__(256) void solver_update_kernel(float* __restrict__ 
     }
 }
 
+// solver_update_kernel under a per-step guidance scale: CFG always, the scale of the launch is
+// cfg_table[i] with i the index the launch reads sigma at (the corrector: *step - 1, the scale its predictor used).  MODE
+// 0 / 1 / 2 as above, MODE 3: Euler, in the roundings euler_cfg_kernel compiles to (the comment above).  An entry that is
+// exactly 1.0f is an unguided step: v = v_c, and the unconditional half of `pred` is NOT loaded -- the engine did not
+// compute it (engine.py: skip_unguided_branch) and what lies there is stale.  Both halves of z still move by v, each in
+// its own rounding, and vh keeps v.  With any other entry every statement is solver_update_kernel's with use_cfg = 1, so
+// a table of one value s != 1 gives that kernel's bits with cfg_scale = s.
+template <int MODE>
+__global__ __launch_bounds__(256) void solver_update_sched_kernel(float* __restrict__ z, bf16* __restrict__ zm,
+                                                                  const bf16* __restrict__ pred, float* __restrict__ vh,
+                                                                  const float* __restrict__ sigma,
+                                                                  const float* __restrict__ cfg_table,
+                                                                  const int32_t* __restrict__ step, int n_steps,
+                                                                  int n_frames, int64_t elems, int pred_type) {
+#pragma clang fp contract(off)
+    const int st = *step;
+    if (MODE == 2 ? (st < 1 || st >= n_steps) : (st < 0 || st >= n_steps)) return;   // past either table: a no-op
+    const int s0 = MODE == 2 ? st - 1 : st;
+    const float sg = sigma[s0], sg_next = sigma[s0 + 1];
+    const float cfg_scale = cfg_table[s0];
+    const bool guided = cfg_scale != 1.0f;
+    const float dt = sg_next - sg;
+    const float inv = 1.0f / (1.0f - (MODE == 2 ? sg_next : sg));
+    const bool two_step = MODE == 0 && st >= 1;
+    const float ratio = two_step ? 0.5f * dt / (sg - sigma[st - 1]) : 0.f;
+    const bool euler_tail = MODE == 1 && st == n_steps - 1;
+    const int64_t total = (int64_t)(n_frames / 2) * elems;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t iu = i + total;
+        float zc = z[i], zu = z[iu];
+        float v0 = 0.f;
+        float zpc = zc, zpu = zu;   // the state the prediction was made from
+        if (MODE == 2) {
+            v0 = vh[i];
+            zpc = __builtin_fmaf(dt, v0, zc);
+            zpu = __builtin_fmaf(dt, v0, zu);
+        }
+        float vc = bf2f(pred[i]);
+        if (pred_type == VGPT_PRED_X1) vc = (vc - zpc) * inv;
+        if (guided) {
+            float vu = bf2f(pred[iu]);
+            if (pred_type == VGPT_PRED_X1) vu = (vu - zpu) * inv;
+            vc = __builtin_fmaf(cfg_scale, vc - vu, vu);
+        }
+        if (MODE == 0) {
+            float ve = vc;
+            if (two_step) ve = __builtin_fmaf(ratio, vc - vh[i], vc);
+            vh[i] = vc;
+            zc = zc + dt * ve;
+            zu = __builtin_fmaf(dt, ve, zu);
+        } else if (MODE == 1) {
+            if (!euler_tail) {
+                vh[i] = vc;
+                zm[i] = f2bf(__builtin_fmaf(dt, vc, zc));
+                zm[iu] = f2bf(__builtin_fmaf(dt, vc, zu));
+                continue;
+            }
+            zc = zc + dt * vc;
+            zu = __builtin_fmaf(dt, vc, zu);
+        } else if (MODE == 2) {
+            const float hh = 0.5f * dt, vs = v0 + vc;
+            zc = __builtin_fmaf(hh, vs, zc);
+            zu = __builtin_fmaf(hh, vs, zu);
+        } else {
+            zc = zc + dt * vc;
+            zu = __builtin_fmaf(dt, vc, zu);
+        }
+        z[i] = zc;
+        zm[i] = f2bf(zc);
+        z[iu] = zu;
+        zm[iu] = f2bf(zu);
+    }
+}
+
 __global__ void advance_kernel(int32_t* step) { *step += 1; }
 
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ src,
@@ -528,6 +603,43 @@ VGPT_EXPORT int vgpt_sampler_update(float* z, void* z_model, const void* pred, f
     else SU_LAUNCH(2);
 #undef SU_LAUNCH
     VGPT_CHECK_LAUNCH("vgpt_sampler_update");
+    return VGPT_OK;
+}
+
+VGPT_EXPORT int vgpt_sampler_update_sched(float* z, void* z_model, const void* pred, float* v_hist, const float* sigma,
+                                          const float* cfg_table, const int32_t* step, int n_steps, int n_frames,
+                                          int64_t elems, int pred_type, int solver, int stage, void* stream) {
+    VGPT_REQUIRE(solver == VGPT_SOLVER_EULER || solver == VGPT_SOLVER_AB2 || solver == VGPT_SOLVER_HEUN, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update_sched: unknown solver %d", solver);
+    VGPT_REQUIRE(stage == 0 || stage == 1, VGPT_ERR_INVALID, "vgpt_sampler_update_sched: unknown stage %d", stage);
+    VGPT_REQUIRE(stage == 0 || solver == VGPT_SOLVER_HEUN, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update_sched: stage %d of the one-stage solver %d", stage, solver);
+    VGPT_REQUIRE(z && z_model && pred && sigma && step, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update_sched: null pointer (z %p, z_model %p, pred %p, sigma %p, step %p)", (void*)z, z_model,
+                 pred, (const void*)sigma, (const void*)step);
+    VGPT_REQUIRE(cfg_table, VGPT_ERR_INVALID, "vgpt_sampler_update_sched: null cfg_table (%p)", (const void*)cfg_table);
+    VGPT_REQUIRE(v_hist || solver == VGPT_SOLVER_EULER, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update_sched: null v_hist with solver %d (only Euler keeps no history)", solver);
+    VGPT_REQUIRE(n_steps > 0, VGPT_ERR_INVALID, "vgpt_sampler_update_sched: n_steps %d <= 0", n_steps);
+    VGPT_REQUIRE(n_frames >= 0 && elems >= 0, VGPT_ERR_INVALID, "vgpt_sampler_update_sched: bad shape (%d frames of %lld)",
+                 n_frames, (long long)elems);
+    VGPT_REQUIRE(pred_type == VGPT_PRED_V || pred_type == VGPT_PRED_X1, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update_sched: unknown prediction type %d", pred_type);
+    VGPT_REQUIRE(n_frames % 2 == 0, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update_sched: CFG needs an even number of frames (got %d)", n_frames);
+    if (n_frames == 0 || elems == 0) return VGPT_OK;
+    const int64_t total = (int64_t)(n_frames / 2) * elems;
+    int grid = (int)std::min<int64_t>(cdiv(total, 256), 2048);
+#define SUS_LAUNCH(MODE)                                                                                        \
+    hipLaunchKernelGGL(solver_update_sched_kernel<MODE>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z,      \
+                       (bf16*)z_model, (const bf16*)pred, v_hist, sigma, cfg_table, step, n_steps, n_frames, elems, \
+                       pred_type)
+    if (solver == VGPT_SOLVER_EULER) SUS_LAUNCH(3);
+    else if (solver == VGPT_SOLVER_AB2) SUS_LAUNCH(0);
+    else if (stage == 0) SUS_LAUNCH(1);
+    else SUS_LAUNCH(2);
+#undef SUS_LAUNCH
+    VGPT_CHECK_LAUNCH("vgpt_sampler_update_sched");
     return VGPT_OK;
 }
 

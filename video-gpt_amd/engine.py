@@ -23,8 +23,8 @@ import torch
 from . import ops
 from .layout import TokenLayout
 from .ops import BF16, VgptError
-from .step_plan import (_hoist_plan, _rows, clip_pass_rows, count_left_pads, pack_left_padded,  # noqa: F401 (re-exported)
-                        plan_step_rows, sp_final_layer_owners, sp_shares)
+from .step_plan import (_hoist_plan, _rows, clip_pass_rows, conditional_live_rows, count_left_pads,  # noqa: F401 (re-exported)
+                        pack_left_padded, plan_step_rows, sp_final_layer_owners, sp_shares)
 
 
 _FOLDED = weakref.WeakKeyDictionary()   # model -> (key, qkv weights, gate_up weights) with the RMSNorm gains folded in
@@ -76,7 +76,8 @@ class StaticDenoiser:
                  prediction_type: str = "v", sigma: Optional[torch.Tensor] = None, pack_padding: bool = True,
                  reuse_condition_prefix: bool = False, hoist_special_rows: bool = True,
                  attention_precision: str = "bf16", fuse_norms: Optional[bool] = None, linear_precision: str = "bf16",
-                 sequence_parallel: bool = False, sp_group=None, solver: str = "euler"):
+                 sequence_parallel: bool = False, sp_group=None, solver: str = "euler", guidance_scales=None,
+                 skip_unguided_branch: Optional[bool] = None):
         # solver: "euler" (default), "ab2" or "heun" (DESIGN.md section 5); an unknown name is refused, naming it, before
         # anything else is looked at
         self.solver = ops.solver_id(solver)
@@ -183,6 +184,7 @@ class StaticDenoiser:
         self._alloc_workspaces()
         self._set_projection_mode(fuse_norms)
         self._alloc_step_buffers()
+        self._set_guidance(guidance_scales, skip_unguided_branch, plan)
         self._initial_passes()
 
     # ---- allocation, once per engine ------------------------------------------------------------------------------------
@@ -214,10 +216,90 @@ class StaticDenoiser:
         self.te_h = e(nf, H)
         self.temb = e(nf, H)
         self.mod = e(nf, 2 * H)
-        self.graph = self.graph_last = None
+        self._drop_graphs()
         self.time_qkv = None   # hoisting: (steps, layers, n_frames, 3H) q/k/v rows of the time tokens of every step
         self.mod_all = None    # (steps, 1, n_frames, 2H) adaLN shift / scale of the final layer for every step (_mod_pass)
         self.steps_taken = 0
+
+    def _drop_graphs(self):
+        """Forget every captured step: `graph` (and Heun's Euler-shaped final step, `graph_last`), and under a guidance
+        schedule that skips rows the same pair for the steps that run the conditional rows only."""
+        self.graph = self.graph_last = self.graph_c = self.graph_c_last = None
+
+    # ---- per-step guidance scale (DESIGN.md section 5b) -----------------------------------------------------------------
+    def _set_guidance(self, scales, skip, plan):
+        """guidance_scales: None (one scale for the clip, `img_cfg_scale`: nothing here changes what is launched), or one
+        image-CFG scale per step (scheduler.guidance_table).  The table lives at a stable device address and every update
+        launch reads its entry by the device step counter (vgpt_sampler_update_sched); the host keeps unguided[i] =
+        (scales[i] == 1.0).  In an unguided step the guided velocity is the conditional one, so with skipping such a step
+        runs the conditional rows only (step_plan.conditional_live_rows): Mc rows of the sequence assembly, the decoder
+        layers, the attention (its own segments and plan) and the final layer; the unconditional rows of hid / ctx / act /
+        pred are neither read nor written.  skip_unguided_branch: None = skip where the layout gives such a range and the
+        engine is not sharded; True = the same, refused otherwise; False = never (the kernel still takes v_c on the 1.0
+        entries, so False and None differ only in which rows were computed)."""
+        self.gtable, self.unguided, self.cr = None, None, None
+        if scales is None:
+            if skip:
+                raise VgptError("StaticDenoiser: skip_unguided_branch=True without guidance_scales (no step is unguided)")
+            return
+        if not self.use_cfg:
+            raise VgptError("StaticDenoiser: guidance_scales with use_img_cfg=False: there is nothing to schedule")
+        t = torch.as_tensor(scales, dtype=torch.float32).reshape(-1).cpu()
+        if self.sigma is not None and t.numel() != self.num_steps:
+            raise VgptError(f"StaticDenoiser: guidance_scales holds {t.numel()} scales, the sigma table has "
+                            f"{self.num_steps} steps")
+        if not bool(torch.isfinite(t).all()):
+            raise VgptError(f"StaticDenoiser: non-finite guidance scale in {t.tolist()}")
+        self.gtable = t.to(self.dev).contiguous()
+        self.unguided = [v == 1.0 for v in t.tolist()]
+        if skip is False:
+            return
+        why = None
+        cr = conditional_live_rows(plan, plan.attention_mask, self.nf)
+        if self.sp is not None:
+            why = "a sequence-parallel engine cuts its shares over all live rows"
+        elif cr is None:
+            why = ("the conditional sequence's live rows are no leading range of their own (an unpacked batch, a pre-packed "
+                   "mask, or one sequence)")
+        elif cr[2] * 2 != self.nf:
+            why = f"the first packed sequence holds {cr[2]} of the {self.nf} latent frames, not the conditional half"
+        if why is not None:
+            if skip:
+                raise VgptError(f"StaticDenoiser: skip_unguided_branch=True cannot be honoured: {why}")
+            return
+        a, e, ncf, seg = cr
+        Mc = e - a
+        nq, nk, hd = self.heads
+        cut = lambda t_: t_[:, :Mc]                       # leading rows of a (1, rows, .) workspace: a contiguous view
+        c = SimpleNamespace(Mc=Mc, nf=ncf, seg=seg, hid=cut(self.hid), nrm=cut(self.nrm), ctx=cut(self.ctx), act=cut(self.act),
+                            rope=(self.rope_a[0][:Mc], self.rope_a[1][:Mc]), ids=self.ids_a[:, :Mc].contiguous(),
+                            x_rows=self.x_rows_a[:ncf], t_rows=None if self.t_rows_a is None else self.t_rows_a[:ncf],
+                            n_cond=sum(1 for r in plan.cond_rows if r < e), ws=None, mx=None,
+                            # fp8 attention: the rows behind the range that share its last 32-key quantisation block
+                            tail=(e, min(self.L, (e + 31) // 32 * 32)))
+        if self.fuse is not None:
+            # the folded RMSNorms at Mc rows, with a workspace of their own; where the GEMMs have no folded form at that
+            # row count (norm_workspace_bytes is 0) the conditional-rows steps keep the separate RMSNorm kernels
+            wa = ops.norm_workspace_bytes(Mc, self.H, nq * hd)
+            wb = ops.norm_workspace_bytes(Mc, self.H, self.cfg.intermediate_size)
+            if wa > 0 and wb > 0:
+                c.ws = ops.norm_workspace(max(wa, wb), self.dev)
+        if self.mx8 is not None:   # the row quantisers' records at Mc rows; the weights' records are the engine's
+            c.mx = {k: ops.Mx8Tensor(Mc, v.K, self.dev) for k, v in self.mx8.items() if k.startswith("a_")}
+        if not self.S:
+            # one q/k/v buffer, every row rewritten by a full step before it is read.  A conditional-rows step that comes
+            # first leaves the rest unwritten, and a key tile that straddles row Mc is loaded whole: masked keys must be
+            # finite
+            self.qkv.zero_()
+        self.cr = c
+
+    def step_rows(self, index: int) -> int:
+        """Live rows step `index` of the table computes: the conditional rows in an unguided step of an engine that skips,
+        all of them otherwise."""
+        return self.cr.Mc if self._cond(index) else self.Ma
+
+    def _cond(self, index: int) -> bool:
+        return self.cr is not None and 0 <= index < len(self.unguided) and self.unguided[index]
 
     def _alloc_workspaces(self):
         """Activations and q/k/v of the per-step forward: this rank's share of the live rows (sharded), the live rows behind
@@ -443,7 +525,7 @@ class StaticDenoiser:
         wq, wgu = folded_weights(self.model)
         if wq is not self.fuse["wq"] or wgu is not self.fuse["wgu"]:   # re-allocated (other shapes): the graph read the old ones
             self.fuse["wq"], self.fuse["wgu"] = wq, wgu
-            self.graph = self.graph_last = None
+            self._drop_graphs()
 
     def quantize_weights(self):
         """linear_precision "fp8": every decoder layer's qkv / o / gate_up / down weights into their MX-fp8 records, from the
@@ -460,6 +542,9 @@ class StaticDenoiser:
 
     def set_sigma(self, sigma: torch.Tensor):
         """A new sigma table on a built engine: everything that depends on the step index alone is recomputed."""
+        if self.gtable is not None and sigma.numel() - 1 != self.gtable.numel():
+            raise VgptError(f"StaticDenoiser.set_sigma: a sigma table of {sigma.numel() - 1} steps on an engine whose "
+                            f"guidance table holds {self.gtable.numel()} scales")
         self.sigma = sigma.to(self.dev, torch.float32).contiguous()
         self.num_steps = self.sigma.numel() - 1
         self._mod_pass()
@@ -477,7 +562,7 @@ class StaticDenoiser:
         shape = (T, 1, self.nf, 2 * H)
         if self.mod_all is None or tuple(self.mod_all.shape) != shape:
             self.mod_all = e(*shape)          # a captured graph reads this buffer: re-allocating invalidates it
-            self.graph = self.graph_last = None
+            self._drop_graphs()
         self.mod_all.copy_(mod.view(T, 1, 1, 2 * H).expand(*shape))
 
     # ---- special-row hoisting ------------------------------------------------------------------------------------
@@ -525,7 +610,7 @@ class StaticDenoiser:
         shape = (T, self.cfg.num_hidden_layers, nf, W)
         if self.time_qkv is None or tuple(self.time_qkv.shape) != shape:
             self.time_qkv = e(*shape)      # a captured graph reads this buffer: re-allocating invalidates it
-            self.graph = self.graph_last = None
+            self._drop_graphs()
         seg = ((0, 0, Lp),)
 
         def keep(li):
@@ -626,12 +711,32 @@ class StaticDenoiser:
         self.steps_taken = 0
 
     # ---- one denoise forward: z_model, ts -> pred ----
-    def _step_head(self, from_tables: bool):
+    def _step_head(self, from_tables: bool, c=None):
         """Sequence assembly of the live rows (all of them, on every rank): token embeddings, condition patches, time tokens
-        (or, hoisted, the time rows' q/k/v of this step dropped into qkv_full), noisy patches."""
+        (or, hoisted, the time rows' q/k/v of this step dropped into qkv_full), noisy patches.  c (self.cr): the conditional
+        rows and frames only."""
         m, H, S = self.model, self.H, self.S
         hid = self.hid if self.sp is None else self.hid_all
         seq2d = hid.view(-1, H)
+        if c is not None:
+            if not self.hoist:
+                ops.embed_gather(c.ids, m.llm.embed_tokens.weight, out=c.hid)
+            if not S and c.n_cond:
+                ops.patch_embed(self.cond[:c.n_cond], m.input_x_embedder.proj.weight, m.input_x_embedder.proj.bias,
+                                m.pos_embed[0], self.cond_rows[:c.n_cond], seq2d, m.pos_embed_max_size)
+            if not (from_tables and self.hoist):
+                ops.timestep_sinusoid(self.ts, m.time_token.freqs(self.dev), out=self.temb_sin)
+            if self.hoist:   # (the time rows sit below S, cached rows: every frame's are dropped in, as in a full step)
+                if self.time_qkv is None:
+                    raise VgptError("StaticDenoiser: set_sigma() must run before the first step")
+                ops.sampler_copy_step_rows(self.time_qkv, self.time_dst, self.step)
+            else:
+                tt = m.time_token.mlp
+                ops.linear_small(self.temb_sin[:c.nf], tt[0].weight, tt[0].bias, post_act=ops.ACT_SILU, out=self.tt_h[:c.nf])
+                ops.linear_small(self.tt_h[:c.nf], tt[2].weight, tt[2].bias, out=seq2d, out_row=c.t_rows, ldo=H)
+            ops.patch_embed(self.z_model[:c.nf], m.x_embedder.proj.weight, m.x_embedder.proj.bias, m.pos_embed[0], c.x_rows,
+                            seq2d, m.pos_embed_max_size)
+            return
         if not self.hoist:   # a hoisted step's live rows are image rows only: the patch embedding below writes every one
             ops.embed_gather(self.ids_a, m.llm.embed_tokens.weight, out=hid)
         if not S:
@@ -649,16 +754,20 @@ class StaticDenoiser:
         ops.patch_embed(self.z_model, m.x_embedder.proj.weight, m.x_embedder.proj.bias, m.pos_embed[0], self.x_rows_a, seq2d,
                         m.pos_embed_max_size)
 
-    def _step_tail(self, from_tables: bool):
+    def _step_tail(self, from_tables: bool, c=None):
         """Final norm, the final layer's adaLN modulation (from the per-clip table, or the small MLPs on self.ts), final layer
         + unpatchify into `pred`.  Sharded: each rank runs the final layer on the frames it owns rows of, and one all-gather
-        (owner-selected per element) leaves the full `pred` on every rank."""
+        (owner-selected per element) leaves the full `pred` on every rank.  c (self.cr): the conditional rows and frames
+        only; the unconditional half of `pred` keeps what it held."""
         m, H, sp = self.model, self.H, self.sp
-        if sp is None:
+        hid = self.hid
+        if c is not None:
+            (f0, f1), nrm_all, nrm, pred, hid = (0, c.nf), c.nrm, c.nrm, self.pred, c.hid
+        elif sp is None:
             (f0, f1), nrm_all, nrm, pred = (0, self.nf), self.nrm, self.nrm, self.pred
         else:
             (f0, f1), nrm_all, nrm, pred = self.sp_frames, self.nrm_all, self.nrm_all[:, sp["a"]:sp["b"]], self.pred_loc
-        ops.rmsnorm(self.hid, m.llm.norm.weight, m.llm.norm.variance_epsilon, out=nrm)
+        ops.rmsnorm(hid, m.llm.norm.weight, m.llm.norm.variance_epsilon, out=nrm)
         # t_embedder + adaLN modulation: every frame of a step carries the same t (LVM/scheduler.py:169), so one row is
         # computed and broadcast (the small-M kernel re-reads its input rows for every output column)
         if from_tables:
@@ -679,13 +788,28 @@ class StaticDenoiser:
             every = SPM.all_gather_flat(self.pred_loc, sp["group"])          # (P, elements of pred)
             torch.gather(every, 0, self.sp_owner, out=self.pred.view(1, -1))
 
-    def forward_step(self, from_tables: bool = False):
+    def forward_step(self, from_tables: bool = False, cond: bool = False):
         """from_tables: the step is sigma[*step] of the table (sampler_step), so everything that depends on the step
-        alone comes from the per-clip passes; otherwise `self.ts` may hold any timesteps."""
+        alone comes from the per-clip passes; otherwise `self.ts` may hold any timesteps.  cond: the conditional rows only
+        (self.cr; an unguided step of a guidance schedule) -- the same launches on the leading Mc live rows, the first
+        sequence's attention segment, the first half of the frames."""
         from_tables = from_tables and self.mod_all is not None
-        self._step_head(from_tables)
+        c = self.cr if cond else None
+        if cond and c is None:
+            raise VgptError("StaticDenoiser.forward_step: cond=True on an engine that does not skip the unconditional rows")
+        self._step_head(from_tables, c)
         nq, nk, hd = self.heads
         S, pm, ctx, rows, seg, rope = self.S, self.pm, self.ctx, self.attn_item_rows, self.seg_a, self.rope_a
+        hid, nrm, act, fz, mx, n_live = self.hid, self.nrm, self.act, self.fuse, self.mx8, None
+        if c is not None:
+            # ctx stays the full buffer for the attention launches (they address it by absolute row and write the rows of
+            # `seg` only); the projections read its leading rows
+            hid, nrm, act, seg, rope, n_live = c.hid, c.nrm, c.act, c.seg, c.rope, c.Mc
+            if fz is not None:
+                fz = None if c.ws is None else {**fz, "rstd_in": fz["rstd_in"][:c.Mc], "rstd_post": fz["rstd_post"][:c.Mc],
+                                                "ws": c.ws}
+            if mx is not None:
+                mx = {**mx, **c.mx, "rstd": mx["rstd"][:c.Mc]}
         if self.sp is not None:
             rope = tuple(t_[self.sp["a"]:self.sp["b"]] for t_ in rope)
             # (one fused buffer serves every layer when no prefix is cached: _sp_plan)
@@ -693,36 +817,64 @@ class StaticDenoiser:
                                                     lambda li: self.qkv_full[li % len(self.qkv_full)], S, pm, seg, ctx,
                                                     item_rows=rows)
         elif S:
-            qkv_dst = lambda li: self.qkv_full[li][S:]       # this step's q/k/v rows, behind the cached prefix
+            # this step's q/k/v rows, behind the cached prefix (n_live: the conditional rows only)
+            qkv_dst = lambda li: self.qkv_full[li][S:] if n_live is None else self.qkv_full[li][S:S + n_live]
 
             def attention(li):
                 full = self.qkv_full[li].view(1, self.L, -1)
                 if self.attn_fp8:
-                    # the prefix rows were quantised once by prefill(); a step re-quantises from the first row it writes
+                    # the prefix rows were quantised once by prefill(); a step re-quantises from the first row it writes.
+                    # A conditional-rows step (section 5b) leaves the unconditional rows of qkv_full as the last full step
+                    # (or the zero fill) left them, and fp8_from on re-quantises those too: stale but finite values that
+                    # no conditional row attends to (conditional_live_rows checked it).  They are harmless to the scores,
+                    # but V takes one block scale per 32 keys and column: where the range does not end on a multiple of 32
+                    # (the prefix-only and no-prefix layouts) its last keys share a scale with the rows behind it, so those
+                    # rows of the straddling block are zeroed first and the step's result is a function of the conditional
+                    # rows alone.  (A full step has the unconditional keys there instead: in such a layout skipping on and
+                    # off agree within the fp8 tolerance, not bit for bit.)
+                    if c is not None and c.tail[1] > c.tail[0]:
+                        self.qkv_full[li][c.tail[0]:c.tail[1]].zero_()
                     ops.attention_qkv_fp8_hd(full, pm, nq, nk, hd, out=ctx, q_start=S, segments=seg,
                                           workspace=self.fp8_ws[li], quant_from=self.fp8_from)
                 else:
                     ops.attention_qkv_range(full, pm, nq, nk, hd, S, ctx, segments=seg, item_rows=rows)
         else:
-            qkv_dst = lambda li: self.qkv
+            qkv_dst = lambda li: self.qkv if n_live is None else self.qkv[:, :n_live]
 
             def attention(li):
                 if self.attn_fp8:
+                    if c is not None and c.tail[1] > c.tail[0]:   # as above: the straddling 32-key block of V
+                        self.qkv[0, c.tail[0]:c.tail[1]].zero_()
                     ops.attention_qkv_fp8_hd(self.qkv, pm, nq, nk, hd, out=ctx, segments=seg)
                 elif seg is not None:
                     ops.attention_qkv_range(self.qkv, pm, nq, nk, hd, 0, ctx, segments=seg, item_rows=rows)
                 else:
                     ops.attention_qkv(self.qkv, pm, nq, nk, hd, out=ctx)
-        self._layers(self.hid, self.nrm, ctx, self.act, rope, qkv_dst, attention, fz=self.fuse, mx=self.mx8)
-        self._step_tail(from_tables)
+        self._layers(hid, nrm, ctx if c is None else c.ctx, act, rope, qkv_dst, attention, fz=fz, mx=mx)
+        self._step_tail(from_tables, c)
 
-    def sampler_step(self, last: bool = True):
+    def sampler_step(self, last: bool = True, cond: bool = False):
         """LVM/scheduler.py:168-204 for one i: timesteps, model call, x1->v, CFG, update, i += 1.  Euler and ab2: one model
         call and one update kernel.  Heun (`last` False: not the final step of the table): model call, predictor, i += 1,
         model call at sigma[i+1] on bf16(z + h v), corrector -- the step tables are read by *step, so the second call reads
         index i + 1 <= N - 1; the final step (sigma[N] = 1) is the Euler-shaped one."""
         ops.sampler_set_timesteps(self.sigma, self.step, self.ts)
-        self.forward_step(from_tables=True)
+        self.forward_step(from_tables=True, cond=cond)
+        if self.gtable is not None:
+            # a guidance schedule: the same steps with the update that reads the step's scale from the table.  cond: an
+            # unguided step on the conditional rows only -- both model calls of a Heun step are of the step's kind
+            sched = lambda stage: ops.sampler_update_sched(self.z, self.z_model, self.pred, self.v_hist, self.sigma,
+                                                           self.gtable, self.step, self.pred_type, self.solver, stage)
+            if self.solver == ops.SOLVER_HEUN and not last:
+                sched(0)
+                ops.sampler_advance(self.step)
+                ops.sampler_set_timesteps(self.sigma, self.step, self.ts)
+                self.forward_step(from_tables=True, cond=cond)
+                sched(1)
+                return
+            sched(0)
+            ops.sampler_advance(self.step)
+            return
         upd = (self.z, self.z_model, self.pred, self.v_hist, self.sigma, self.step, self.pred_type, self.use_cfg,
                self.cfg_scale)
         if self.solver == ops.SOLVER_HEUN and not last:
@@ -739,25 +891,26 @@ class StaticDenoiser:
                                  self.cfg_scale)
         ops.sampler_advance(self.step)
 
-    def _step_then_capture(self, restore: bool, last: bool = True):
+    def _step_then_capture(self, restore: bool, last: bool = True, cond: bool = False):
         """One eager step (kernels set their launch attributes on first use, which a capture cannot record), then the capture
         of a step, which records without executing.  restore: the eager step leaves no trace in the sampler state (the
         velocity history included: an ab2 step in the middle of a clip reads what the step before it wrote).  Heun keeps two graphs: the
-        two-call step (`graph`) and the Euler-shaped final step (`graph_last`); the other solvers have `graph` alone."""
+        two-call step (`graph`) and the Euler-shaped final step (`graph_last`); the other solvers have `graph` alone.  An
+        engine that skips the unconditional rows keeps the same pair once more for its conditional-rows steps (`graph_c`,
+        `graph_c_last`): one graph per (kind, Heun-last), each captured at the first step of its kind."""
         saved = (self.z.clone(), self.z_model.clone(), self.step.clone()) if restore else None
         hist = self.v_hist.clone() if restore and self.v_hist is not None else None
-        self.sampler_step(last)
+        self.sampler_step(last, cond)
         torch.cuda.current_stream().synchronize()
         if restore:
             self.z.copy_(saved[0]); self.z_model.copy_(saved[1]); self.step.copy_(saved[2])
             if hist is not None:
                 self.v_hist.copy_(hist)
             torch.cuda.current_stream().synchronize()
-        graph = ops.HipGraph().capture(lambda: self.sampler_step(last))
-        if self._two_graphs() and last:
-            self.graph_last = graph
-        else:
-            self.graph = graph
+        setattr(self, self._graph_slot(last, cond), ops.HipGraph().capture(lambda: self.sampler_step(last, cond)))
+
+    def _graph_slot(self, last: bool, cond: bool) -> str:
+        return ("graph_c" if cond else "graph") + ("_last" if self._two_graphs() and last else "")
 
     def _two_graphs(self) -> bool:
         return self.solver == ops.SOLVER_HEUN
@@ -770,7 +923,7 @@ class StaticDenoiser:
         """Capture one sampler step into a hipGraph (must run on a non-default stream)."""
         if self.sp is not None:
             raise VgptError("StaticDenoiser.capture: a sequence-parallel engine runs eagerly (its exchanges are not captured)")
-        self._step_then_capture(restore=True, last=self._is_last(self.steps_taken))
+        self._step_then_capture(restore=True, last=self._is_last(self.steps_taken), cond=self._cond(self.steps_taken))
         return self
 
     def run(self, num_steps: Optional[int] = None, use_graph: bool = True):
@@ -782,13 +935,14 @@ class StaticDenoiser:
         self.steps_taken += n
         use_graph = use_graph and self.sp is None   # sharded engines run eagerly: collectives are not captured (yet)
         for index in range(first, first + n):
-            last = self._is_last(index)   # by the absolute index: run(k) then run(N - k) is run(N)
+            # by the absolute index: run(k) then run(N - k) is run(N), also across a boundary between step kinds
+            last, cond = self._is_last(index), self._cond(index)
             if not use_graph:
-                self.sampler_step(last)
+                self.sampler_step(last, cond)
                 continue
-            graph = self.graph_last if self._two_graphs() and last else self.graph
+            graph = getattr(self, self._graph_slot(last, cond))
             if graph is None:
-                self._step_then_capture(restore=False, last=last)   # the eager step counts as a real one
+                self._step_then_capture(restore=False, last=last, cond=cond)   # the eager step counts as a real one
             else:
                 graph.replay()
         return self.z

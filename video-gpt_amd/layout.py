@@ -102,18 +102,24 @@ class TokenLayout:
         return self
 
     # ---- the dense mask (reference tensor form) ---------------------------------------------------------------------
+    def visible_block(self, q0: int, q1: int, k0: int, k1: int, row: int = 0) -> np.ndarray:
+        """The rule of the module docstring on query rows [q0, q1) x key columns [k0, k1) of batch row `row`: a
+        (q1 - q0, k1 - k0) bool array, without the rest of the (L, L) mask."""
+        b = row
+        q = lambda a: a[b, q0:q1][:, None]
+        k = lambda a: a[b, k0:k1][None, :]
+        rows = np.arange(q0, q1, dtype=np.int64)[:, None]
+        vis = (k(self.kind) == CLEAN) & (q(self.seq) == k(self.seq)) & (rows >= k(self.thr))
+        vis |= (k(self.kind) == NOISY) & (q(self.kind) == NOISY) & (q(self.grp) == k(self.grp)) & \
+               (q(self.oc) >= k(self.oc)) & ((k(self.sub) == 0) | (k(self.sub) == q(self.sub)))
+        vis |= (q(self.kind) == PAD)
+        return vis
+
     def to_bool(self) -> np.ndarray:
         B, L = self.B, self.L
         out = np.zeros((B, L, L), dtype=np.bool_)
-        q = np.arange(L, dtype=np.int64)[:, None]
         for b in range(B):
-            kq, kk = self.kind[b][:, None], self.kind[b][None, :]
-            vis = (kk == CLEAN) & (self.seq[b][:, None] == self.seq[b][None, :]) & (q >= self.thr[b][None, :])
-            vis |= (kk == NOISY) & (kq == NOISY) & (self.grp[b][:, None] == self.grp[b][None, :]) & \
-                   (self.oc[b][:, None] >= self.oc[b][None, :]) & \
-                   ((self.sub[b][None, :] == 0) | (self.sub[b][None, :] == self.sub[b][:, None]))
-            vis |= (kq == PAD)
-            out[b] = vis
+            out[b] = self.visible_block(0, L, 0, L, row=b)
         return out
 
     def to_bool_tensor(self):

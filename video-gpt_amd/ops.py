@@ -913,6 +913,31 @@ def sampler_update(z: torch.Tensor, z_model: torch.Tensor, pred: torch.Tensor, v
          int(solver), int(stage), _stream())
 
 
+def sampler_update_sched(z: torch.Tensor, z_model: torch.Tensor, pred: torch.Tensor, v_hist: Optional[torch.Tensor],
+                         sigma: torch.Tensor, cfg_table: torch.Tensor, step: torch.Tensor, pred_type: int,
+                         solver: int = SOLVER_EULER, stage: int = 0):
+    """sampler_update with image CFG under a per-step guidance scale (include/vgpt.h: vgpt_sampler_update_sched).
+    cfg_table: fp32, one entry per step of sigma's table, on z's device; an entry of exactly 1.0 is an unguided step, in
+    which the unconditional half of `pred` is not read."""
+    _chk(z, torch.float32, "sampler_update_sched.z"); _chk(z_model, BF16, "sampler_update_sched.z_model")
+    _chk(pred, BF16, "sampler_update_sched.pred"); _chk(cfg_table, torch.float32, "sampler_update_sched.cfg_table")
+    nf = z.shape[0]
+    if z_model.numel() != z.numel() or pred.numel() != z.numel():
+        raise VgptError(f"sampler_update_sched: z_model ({z_model.numel()}) / pred ({pred.numel()}) are not z's "
+                        f"{z.numel()} elements")
+    if cfg_table.numel() != sigma.numel() - 1:
+        raise VgptError(f"sampler_update_sched: cfg_table holds {cfg_table.numel()} scales, the sigma table has "
+                        f"{sigma.numel() - 1} steps")
+    if v_hist is not None:
+        _chk(v_hist, torch.float32, "sampler_update_sched.v_hist")
+        if v_hist.numel() != z.numel() // 2:
+            raise VgptError(f"sampler_update_sched: v_hist holds {v_hist.numel()} values, the guided velocity has "
+                            f"{z.numel() // 2}")
+    call("vgpt_sampler_update_sched", z.data_ptr(), z_model.data_ptr(), pred.data_ptr(), _ptr(v_hist), sigma.data_ptr(),
+         cfg_table.data_ptr(), step.data_ptr(), sigma.numel() - 1, nf, z.numel() // max(nf, 1), pred_type, int(solver),
+         int(stage), _stream())
+
+
 def sampler_copy_step_rows(src: torch.Tensor, dst: torch.Tensor, step: torch.Tensor):
     """src: (n_steps, n_layers, rows, W) contiguous; dst: a (n_layers, rows, W) VIEW whose rows are contiguous (layer
     stride arbitrary).  dst[l] = src[*step][l]."""

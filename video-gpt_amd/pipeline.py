@@ -44,6 +44,12 @@ class LVMPipeline:
         self.linear_precision = "bf16"      # "fp8": MX-fp8 decoder-layer projections in the sampler steps (scheduler.LVMScheduler)
         self.sequence_parallel_engine = False   # True: sharded sampler engine under a sequence-parallel group (scheduler.LVMScheduler)
         self.solver = "euler"               # "ab2" / "heun": second-order sampler steps (scheduler.LVMScheduler)
+        # a per-step image-guidance scale (scheduler.guidance_table): img_guidance_scale inside the sigma
+        # interval (lo, hi) and 1 outside it, or an explicit schedule (num_inference_steps scales, or a callable of sigma).
+        # A round the pipeline itself runs without image guidance (img_guidance_scale == 1, no input images) has nothing to
+        # schedule and runs as it always did; the scheduler, asked directly for a schedule without CFG, refuses
+        self.guidance_interval = None
+        self.guidance_schedule = None
 
     @classmethod
     def from_pretrained(cls, model_name, vae_path: str = None, load_llm_ckpt=True):
@@ -201,7 +207,9 @@ class LVMPipeline:
                                 img_cfg_scale=img_guidance_scale, use_img_cfg=use_img_guidance, use_kv_cache=use_kv_cache,
                                 offload_model=False)
             scheduler = LVMScheduler(num_steps=num_inference_steps, time_shifting_factor=time_shifting_factor,
-                                     solver=self.solver)
+                                     solver=self.solver,
+                                     guidance_interval=self.guidance_interval if use_img_guidance else None,
+                                     guidance_schedule=self.guidance_schedule if use_img_guidance else None)
             scheduler.attention_precision = self.attention_precision
             scheduler.linear_precision = self.linear_precision
             scheduler.sequence_parallel_engine = self.sequence_parallel_engine
@@ -310,7 +318,9 @@ class LVMPipeline:
                 img_cfg_scale=img_guidance_scale, use_img_cfg=use_img_guidance, use_kv_cache=use_kv_cache,
                 offload_model=False, vae=self.vae)
             scheduler = LVMScheduler(num_steps=num_inference_steps, time_shifting_factor=time_shifting_factor,
-                                     solver=self.solver)
+                                     solver=self.solver,
+                                     guidance_interval=self.guidance_interval if use_img_guidance else None,
+                                     guidance_schedule=self.guidance_schedule if use_img_guidance else None)
             scheduler.attention_precision = self.attention_precision
             scheduler.linear_precision = self.linear_precision
             scheduler.sequence_parallel_engine = self.sequence_parallel_engine

@@ -27,14 +27,58 @@ from . import ops
 from .ops import BF16, VgptError
 
 
+def guidance_table(sigma, scale: float, interval=None, schedule=None):
+    """The image-CFG scale of every step of the table `sigma` (N + 1 entries, step i runs at sigma[i]) as an fp32 tensor
+    (N), or None when neither `interval` nor `schedule` is given: the scalar path, one scale for the clip.
+
+    interval = (lo, hi), in the scheduler's own sigma units (0 = noise, 1 = data): entry i is `scale` where
+    lo <= sigma[i] < hi and 1.0 elsewhere (limited-interval guidance, Kynkaanniemi et al. 2024).  schedule: N scales, or a
+    callable of sigma[i].  An entry of exactly 1.0 is an unguided step: the guided velocity is the
+    conditional one, and the fast path does not compute the unconditional rows at all."""
+    if interval is None and schedule is None:
+        return None
+    if interval is not None and schedule is not None:
+        raise VgptError(f"guidance_table: both interval={interval!r} and schedule={schedule!r} given (one of them)")
+    sig = [float(s) for s in torch.as_tensor(sigma).reshape(-1).tolist()]
+    n = len(sig) - 1
+    if n <= 0:
+        raise VgptError(f"guidance_table: a sigma table of {len(sig)} entries has no step")
+    if interval is not None:
+        lo, hi = (float(v) for v in interval)
+        if not lo <= hi:   # also refuses a NaN bound
+            raise VgptError(f"guidance_table: interval lo={lo!r} > hi={hi!r}")
+        vals = [float(scale) if lo <= s < hi else 1.0 for s in sig[:n]]
+    elif callable(schedule):
+        vals = [float(schedule(s)) for s in sig[:n]]
+    else:
+        vals = [float(v) for v in (schedule.tolist() if isinstance(schedule, torch.Tensor) else schedule)]
+        if len(vals) != n:
+            raise VgptError(f"guidance_table: schedule has {len(vals)} entries, num_steps is {n}")
+    out = torch.tensor(vals, dtype=torch.float32)
+    bad = [(i, v) for i, v in enumerate(out.tolist()) if v != v or v in (float("inf"), float("-inf"))]
+    if bad:
+        raise VgptError(f"guidance_table: non-finite scale {bad[0][1]!r} at step {bad[0][0]}")
+    return out
+
+
 class LVMScheduler:
-    def __init__(self, num_steps: int = 50, time_shifting_factor: int = 1, begin_time=None, solver: str = "euler"):
+    def __init__(self, num_steps: int = 50, time_shifting_factor: int = 1, begin_time=None, solver: str = "euler",
+                 guidance_interval=None, guidance_schedule=None):
         ops.solver_id(solver)   # an unknown name is refused here, naming it
         self.solver = solver
+        # a per-step image-CFG scale (guidance_table): the clip's img_cfg_scale inside `guidance_interval` = (lo, hi) of
+        # sigma and 1.0 outside it, or `guidance_schedule` (num_steps scales, or a callable of sigma_i).  Both None: one
+        # scale for the clip, as before.  The fast path skips the unconditional rows in the steps whose scale is exactly 1
+        # (skip_unguided_branch: None = wherever the layout allows it, True = or refuse, False = never); the generic path
+        # applies the per-step scale and skips nothing -- the model call is the caller's.
+        self.guidance_interval = guidance_interval
+        self.guidance_schedule = guidance_schedule
+        self.skip_unguided_branch = None
         self.num_steps = num_steps
         self.time_shift = time_shifting_factor
         t = torch.linspace(0 if begin_time is None else begin_time, 1, num_steps + 1)
         self.sigma = t / (t + time_shifting_factor - time_shifting_factor * t)
+        guidance_table(self.sigma, 1.0, guidance_interval, guidance_schedule)   # a bad schedule is refused here, by value
         self.use_graph = True
         self.pack_padding = True
         self.reuse_condition_prefix = True   # compute the step-invariant condition rows once per clip (engine.py)
@@ -75,6 +119,7 @@ class LVMScheduler:
         from .train import wait_for_pending_update
         wait_for_pending_update(owner)      # a trainer's overlapped AdamW update of these parameters may still be in flight
         self._owner_params = list(owner.parameters())
+        self._table = self._guidance(model_kwargs)
         key = self._engine_key(z, model_kwargs, prediction_type) if self.cache_engines else None
         cache = owner.__dict__.setdefault("_vgpt_engine_cache", {}) if key is not None else None
         if cache is not None and key in cache:
@@ -88,6 +133,16 @@ class LVMScheduler:
             while len(cache) > 2:                # a clip's buffers are a few GB at cfg-2: the last two layouts are kept
                 cache.pop(next(iter(cache)))
         return eng
+
+    def _guidance(self, model_kwargs):
+        """The clip's scale table (guidance_table on this scheduler's sigma and the call's img_cfg_scale), or None."""
+        if self.guidance_interval is None and self.guidance_schedule is None:
+            return None
+        if not model_kwargs.get("use_img_cfg", False):
+            raise VgptError(f"LVMScheduler: guidance_interval={self.guidance_interval!r} / guidance_schedule="
+                            f"{self.guidance_schedule!r} with use_img_cfg=False: there is nothing to schedule")
+        return guidance_table(self.sigma, float(model_kwargs.get("img_cfg_scale", 1.0)), self.guidance_interval,
+                              self.guidance_schedule)
 
     def _engine_key(self, z, model_kwargs, prediction_type):
         """Everything a StaticDenoiser is built from except the condition latents' VALUES; None when the mask is not a
@@ -105,6 +160,8 @@ class LVMScheduler:
                 bool(model_kwargs["use_img_cfg"]), float(model_kwargs["img_cfg_scale"]), prediction_type, tb(self.sigma),
                 self.pack_padding, self.reuse_condition_prefix, self.hoist_special_rows, self.attention_precision,
                 self.linear_precision, self.fuse_norms, str(z[0].device), self.solver,
+                # two guidance schedules never share an engine: its table, step kinds and graphs are the schedule's
+                None if self._table is None else self._table.numpy().tobytes(), self.skip_unguided_branch,
                 # a sharded engine holds this rank's rows and heads of a group of this size
                 self.sequence_parallel_engine, SPM.sp_world(), SPM.sp_rank(),
                 # the GEMM family decided whether the engine folded the RMSNorms (norm_workspace_bytes is 0 under family 1) and
@@ -124,7 +181,8 @@ class LVMScheduler:
                               hoist_special_rows=self.hoist_special_rows,
                               attention_precision=self.attention_precision, linear_precision=self.linear_precision,
                               fuse_norms=self.fuse_norms, sequence_parallel=self.sequence_parallel_engine,
-                              solver=self.solver)
+                              solver=self.solver, guidance_scales=self._table,
+                              skip_unguided_branch=self.skip_unguided_branch)
 
     def __call__(self, z, func, model_kwargs, use_kv_cache: bool = True, offload_kv_cache: bool = True,
                  prediction_type: str = "v", vae=None, noise_level=None):
@@ -195,28 +253,42 @@ class LVMScheduler:
             raise VgptError("image CFG needs the conditional and unconditional halves (an even number of latents)")
         pred_type = ops.PRED_X1 if prediction_type == "x1" else ops.PRED_V
         solver = ops.solver_id(self.solver)
+        # a guidance schedule on this path: the per-step scale is applied and NO rows are skipped (the model call is the
+        # caller's and computes both halves).  x1: the table goes to the update kernel; v: the CFG combination happens
+        # inside func, which gets the step's scale as its img_cfg_scale
+        table = self._guidance(model_kwargs)
+        scales = None if table is None else table.tolist()
+        table_dev = table.to(dev) if kernel_cfg and table is not None else None
         # the guided velocity of the step (ab2: of the previous one when it is read), one CFG half
         v_hist = None if solver == ops.SOLVER_EULER else torch.empty(n // 2 if kernel_cfg else n, elems, dtype=torch.float32,
                                                                     device=dev)
 
-        def evaluate():
+        def evaluate(i=None):
             ops.sampler_set_timesteps(sigma, step, ts)
             z_in = [zm[i].view(shapes[i]) for i in range(n)] if is_list else zm.view(frames[0].shape)
-            pred, _cache = func(z_in, ts, past_key_values=None, prediction_type=prediction_type, **model_kwargs)
+            mk = model_kwargs if scales is None else {**model_kwargs, "img_cfg_scale": scales[i]}
+            pred, _cache = func(z_in, ts, past_key_values=None, prediction_type=prediction_type, **mk)
             if is_list:
                 pred = torch.cat([p.reshape(1, -1) for p in pred], dim=0)
             return pred.reshape(n, elems).to(BF16).contiguous()
 
+        def update(pred, stage=0):
+            if table_dev is not None:
+                ops.sampler_update_sched(zf, zm, pred, v_hist, sigma, table_dev, step, pred_type, solver, stage)
+            else:
+                ops.sampler_update(zf, zm, pred, v_hist, sigma, step, pred_type, kernel_cfg, scale, solver, stage)
+
         for i in range(self.num_steps):
-            pred = evaluate()
+            pred = evaluate(i)
             if solver == ops.SOLVER_HEUN and i < self.num_steps - 1:
-                # predictor -> the model at sigma[i+1] on bf16(z + h v) -> corrector; the last step (sigma = 1) is Euler's
-                ops.sampler_update(zf, zm, pred, v_hist, sigma, step, pred_type, kernel_cfg, scale, solver, 0)
+                # predictor -> the model at sigma[i+1] on bf16(z + h v) -> corrector; the last step (sigma = 1) is Euler's.
+                # Both model calls of the step use the step's scale
+                update(pred, 0)
                 ops.sampler_advance(step)
-                ops.sampler_update(zf, zm, evaluate(), v_hist, sigma, step, pred_type, kernel_cfg, scale, solver, 1)
+                update(evaluate(i), 1)
                 continue
-            if solver == ops.SOLVER_AB2:
-                ops.sampler_update(zf, zm, pred, v_hist, sigma, step, pred_type, kernel_cfg, scale, solver)
+            if solver == ops.SOLVER_AB2 or table_dev is not None:
+                update(pred)
             else:
                 ops.euler_cfg_update(zf, zm, pred, sigma, step, pred_type, kernel_cfg, scale)
             ops.sampler_advance(step)

@@ -249,6 +249,50 @@ def plan_step_rows(input_ids, position_ids, attention_mask, input_image_sizes, d
                     t_rows=_rows(time_emb_inx, row_of, False), row_map=row_map)
 
 
+def _sees(mask, q0: int, q1: int, k0: int, k1: int) -> bool:
+    """Whether any row of [q0, q1) sees a column of [k0, k1) of batch row 0: from a TokenLayout's attributes
+    (TokenLayout.visible_block: its rule on that block alone) or from a dense mask."""
+    if q1 <= q0 or k1 <= k0:
+        return False
+    if not isinstance(mask, TokenLayout):
+        return bool(mask[0, q0:q1, k0:k1].to(torch.bool).any())
+    return bool(mask.visible_block(q0, q1, k0, k1).any())
+
+
+def conditional_live_rows(plan: StepPlan, layout_or_mask, n_frames: int):
+    """The rows a step computes for the FIRST packed sequence alone (with image CFG: the conditional one), or None.
+
+    Returns (row_begin, row_end, n_cond_frames, segments): the leading range [S, S + Mc) of the live rows [S, L) that
+    belongs to the first packed sequence, the number of (leading) noisy frames whose rows lie in it, and the attention-plan
+    segments restricted to it.  A step that needs the first sequence's prediction only (an unguided step of a guidance
+    schedule, engine.py) may run these rows and nothing else: it is checked HERE, from the mask's attributes, that no row of
+    the range sees a live row outside it -- the rows below S it sees are cached, step-invariant ones.
+    None when the live rows of sequence 0 are no such range: an unpacked batch, a pre-packed mask (nothing is known about
+    it), one sequence, frames or time rows that do not split into a leading group inside the range and a rest outside it, or
+    a range that sees out."""
+    if not plan.packed or plan.B != 1 or not isinstance(layout_or_mask, (TokenLayout, torch.Tensor)):
+        return None
+    seg = plan.seg_live if plan.S else plan.seg_all
+    if seg is None or len(seg) < 2:
+        return None
+    S, L = plan.S, plan.L
+    _, a, e = seg[0]
+    if a != S or not (S < e < L) or len(plan.x_rows) != n_frames:
+        return None
+    inside = [a <= x < e for x in plan.x_rows]
+    nc = sum(inside)
+    if nc == 0 or nc == n_frames or not all(inside[:nc]):
+        return None
+    # the time rows of a layout that keeps them live go with their frames (hoisted: they sit below S, written for every frame)
+    if not plan.hoist and [a <= t < e for t in plan.t_rows] != inside:
+        return None
+    if any(x < S for x in plan.x_rows) or (not plan.hoist and any(t < S for t in plan.t_rows)):
+        return None
+    if _sees(layout_or_mask, a, e, e, L):
+        return None
+    return a, e, nc, (seg[0],)
+
+
 def clip_pass_rows(S0: int, nf: int, T: int):
     """The one-sequence per-clip pass of a hoisted layout (StaticDenoiser._clip_pass),
         [prefix 0..S0) | nf `<|diffusion|>` rows | step 0's nf time rows | step 1's | ... | step T-1's],
