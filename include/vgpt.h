@@ -454,6 +454,34 @@ int vgpt_sampler_update(float* z, void* z_model, const void* pred, float* v_hist
 int vgpt_sampler_update_sched(float* z, void* z_model, const void* pred, float* v_hist, const float* sigma,
                               const float* cfg_table, const int32_t* step, int n_steps, int n_frames, int64_t elems,
                               int pred_type, int solver, int stage, void* stream);
+/* The Euler step of vgpt_euler_cfg_update with noise re-injected (the flow-matching counterpart of
+ * DDIM's eta).  i = *step, h = sigma[i+1] - sigma[i], v the guided velocity, eta = eta_table[i] (n_steps fp32 entries,
+ * device memory):
+ *     x0_hat = z - sigma[i] v,   z' = (z + h v) + (1 - sigma[i+1]) ((sqrt(1 - eta^2) - 1) x0_hat + eta eps)
+ * eps = the normal of vgpt_sampler_noise_fill at (seed, stream, step i, element e), e the frame-major element index
+ * within one noise half: all frames without sharing; with use_cfg = 1 (which implies it) or share_halves = 1 the frames
+ * [n/2, n) reuse the numbers of [0, n/2) -- share_halves alone is for callers whose model call combined the CFG halves
+ * already, every frame then moving by its own prediction.  rng: int64[2] in DEVICE memory, {seed, stream}, read by the
+ * kernel: a captured launch serves a new seed without recapture.
+ * With eta_table[i] == 0.0f exactly the launch gives vgpt_euler_cfg_update's bits (with cfg_table:
+ * vgpt_sampler_update_sched's, VGPT_SOLVER_EULER), and so does any eta at 1 - sigma[i+1] == 0, the last step.
+ * cfg_table: null, or n_steps per-step guidance scales in place of cfg_scale with the semantics of
+ * vgpt_sampler_update_sched (an entry of exactly 1.0f: v = v_c, the unconditional half of pred is not loaded); it needs
+ * use_cfg = 1.  No history buffer: only the first-order step takes noise.  With *step outside [0, n_steps) nothing is
+ * written.  VGPT_ERR_INVALID (the offending value in the message): null pointer, n_steps <= 0, negative n_frames or
+ * elems ("bad shape"), odd n_frames with use_cfg or share_halves, unknown pred_type, cfg_table with use_cfg = 0.  Zero
+ * sizes return VGPT_OK.  The entries of eta_table are NOT checked (they are device memory): keeping them in [0, 1] is the
+ * caller's duty -- outside it sqrt(1 - eta^2) is the square root of a negative number and the state becomes NaN
+ * (scheduler.eta_table and StaticDenoiser refuse such a value before it reaches a table). */
+int vgpt_sampler_update_sde(float* z, void* z_model, const void* pred, const float* sigma, const float* cfg_table,
+                            const float* eta_table, const int64_t* rng, const int32_t* step, int n_steps, int n_frames,
+                            int64_t elems, int pred_type, int use_cfg, float cfg_scale, int share_halves, void* stream);
+/* out[e] = eps(seed, stream, step_index, e) for e < n: counter-based standard normals.  Philox4x32-10 (Salmon et al.
+ * 2011) with key (seed low, seed high) and counter (block low, block high, step_index, stream low), block = e >> 2; its
+ * four words w0..w3 give elements 4 block .. 4 block + 3: u1 = ((w0 >> 9) + 0.5) 2^-23, u2 = (w1 >> 8) 2^-24,
+ * r = sqrtf(-2 logf(u1)), (r cospif(2 u2), r sinpif(2 u2)), and the same from (w2, w3); |eps| <= sqrt(48 ln 2).
+ * rng: int64[2] {seed, stream} in device memory.  VGPT_ERR_INVALID: null pointer, n < 0; n == 0 returns VGPT_OK. */
+int vgpt_sampler_noise_fill(float* out, int64_t n, const int64_t* rng, int step_index, void* stream);
 /* *step += 1 */
 int vgpt_sampler_advance(int32_t* step, void* stream);
 /* dst[l][0:slab_bytes] = src[*step][l][0:slab_bytes] for l < n_layers (step clamped to [0, n_steps)); all sizes and

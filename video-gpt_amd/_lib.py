@@ -89,6 +89,8 @@ SIGNATURES = {
     "vgpt_euler_cfg_update": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _I64, c_int, c_int, c_float, _P]),
     "vgpt_sampler_update": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _I64, c_int, c_int, c_float, c_int, c_int, _P]),
     "vgpt_sampler_update_sched": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _I64, c_int, c_int, c_int, _P]),
+    "vgpt_sampler_update_sde": (c_int, [_P] * 8 + [c_int, c_int, _I64, c_int, c_int, c_float, c_int, _P]),
+    "vgpt_sampler_noise_fill": (c_int, [_P, _I64, _P, c_int, _P]),
     "vgpt_sampler_advance": (c_int, [_P, _P]),
     "vgpt_sampler_copy_step_rows": (c_int, [_P, _P, _P, c_int, c_int, _I64, _I64, _I64, _I64, _P]),
     "vgpt_cast_f32_to_bf16": (c_int, [_P, _P, _I64, _P]),

@@ -1,7 +1,9 @@
 // Model-glue kernels around the transformer: token-embedding gather, patch embedding with the
 // cropped 2-D sincos position table, timestep embedding, small-M Linear, final adaLN layer with
-// unpatchify, and the Euler / CFG sampler update. All HBM- or latency-bound; written so the whole
-// denoise step is a fixed sequence of launches that can be captured into one hipGraph.
+// unpatchify, and the Euler / CFG sampler update with its second-order, scheduled-guidance and
+// stochastic forms (the last makes its noise from a counter, so a replayed graph draws fresh
+// numbers). All HBM- or latency-bound; written so the whole denoise step is a fixed sequence of
+// launches that can be captured into one hipGraph.
 //
 // Reference: LVM/model.py:22-83 (modulate, TimestepEmbedder, FinalLayer), :138-154 (PatchEmbedMR),
 // :255-327 (unpatchify, cropped_pos_embed, patch_multiple_resolutions), :399-501 (frame_block_forward),
@@ -422,6 +424,189 @@ __global__ __launch_bounds__(256) void solver_update_sched_kernel(float* __restr
     }
 }
 
+// ---- stochastic Euler step ----------------------------------------------------
+// Counter-based noise: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11: multipliers,
+// Weyl key increments and round function of Random123).  Key = the seed's two words, counter = (block low, block high,
+// step index, stream low word), block = e >> 2 with e the element index inside one CFG half.  One call yields the four
+// normals of elements 4 block .. 4 block + 3 by Box-Muller on (w0, w1) and (w2, w3): a function of (seed, stream, step,
+// element) alone, so a captured step replays fresh numbers every step and every launch shape gives the same ones.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t (&w)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+// u1 = ((w >> 9) + 0.5) 2^-23 in (0, 1) and u2 = (w >> 8) 2^-24 in [0, 1) are exact in fp32; r = sqrtf(-2 logf(u1));
+// (r cospif(2 u2), r sinpif(2 u2)).  The accurate logf / sincospif; every product is one rounding.
+__device__ __forceinline__ void sde_normals(const int64_t* __restrict__ rng, int64_t block, int step, float (&eps)[4]) {
+#pragma clang fp contract(off)
+    const uint64_t seed = (uint64_t)rng[0];
+    uint32_t w[4];
+    philox4x32_10((uint32_t)block, (uint32_t)((uint64_t)block >> 32), (uint32_t)step, (uint32_t)(uint64_t)rng[1],
+                  (uint32_t)seed, (uint32_t)(seed >> 32), w);
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const float u1 = ((float)(w[2 * p] >> 9) + 0.5f) * 0x1p-23f;
+        const float u2 = (float)(w[2 * p + 1] >> 8) * 0x1p-24f;
+        const float r = sqrtf(-2.0f * logf(u1));
+        float s, c;
+        sincospif(2.0f * u2, &s, &c);
+        eps[2 * p] = r * c;
+        eps[2 * p + 1] = r * s;
+    }
+}
+
+__global__ __launch_bounds__(256) void noise_fill_kernel(float* __restrict__ out, int64_t n,
+                                                         const int64_t* __restrict__ rng, int step) {
+    const int64_t blocks = (n + 3) >> 2;
+    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < blocks; b += (int64_t)gridDim.x * blockDim.x) {
+        float eps[4];
+        sde_normals(rng, b, step, eps);
+        const int64_t e = b << 2;
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            if (e + l < n) out[e + l] = eps[l];
+    }
+}
+
+// The Euler step with noise re-injected, eta = eta_table[*step]:
+//   x0_hat = z - sigma_i v,   z' = (z + h v) + (1 - sigma_{i+1}) ((sqrt(1 - eta^2) - 1) x0_hat + eta eps)
+// The Euler part is statement for statement euler_cfg_kernel's in the roundings it compiles to (the comment above
+// solver_update_kernel), with a guidance table solver_update_sched_kernel<3>'s; with eta == 0.0f exactly, or at the last
+// step (1 - sigma_{i+1} == 0), nothing else is computed and those kernels' bits come out.  The noise term of one state
+// element, every rounding spelled out: x0 = fma(-sigma_i, v, z); t = fma(eta, eps, rn(ca x0)), ca = rn(sqrtf(rn(1 -
+// rn(eta eta))) - 1); z' = fma(g, t, z_euler), g = rn(1 - sigma_{i+1}).  Each thread owns one Philox block: four
+// consecutive elements e of one CFG half, and every frame that shares the half's noise (`paired`: the unconditional half
+// under CFG, frames [n/2, n) under share_halves) gets the same eps at the same e.  VEC: 16-byte z and 8-byte bf16
+// accesses, for a half size that is a multiple of 4 on pointers aligned that far; otherwise element by element, the tail
+// thread using the lanes it owns.  Both forms run the same statements per element.
+template <bool VEC>
+__global__ __launch_bounds__(256) void sde_update_kernel(float* __restrict__ z, bf16* __restrict__ zm,
+                                                         const bf16* __restrict__ pred,
+                                                         const float* __restrict__ sigma,
+                                                         const float* __restrict__ cfg_table,
+                                                         const float* __restrict__ eta_table,
+                                                         const int64_t* __restrict__ rng,
+                                                         const int32_t* __restrict__ step, int n_steps, int n_frames,
+                                                         int64_t elems, int pred_type, int use_cfg, float cfg_scale,
+                                                         int share_halves) {
+#pragma clang fp contract(off)
+    const int st = *step;
+    if (st < 0 || st >= n_steps) return;   // past the tables: leave everything untouched
+    const float sg = sigma[st], sg_next = sigma[st + 1];
+    const float eta = eta_table[st];
+    if (cfg_table) cfg_scale = cfg_table[st];
+    const bool guided = use_cfg && !(cfg_table && cfg_scale == 1.0f);   // an entry of exactly 1: v = v_c, pred[iu] not loaded
+    const float dt = sg_next - sg;
+    const float inv = 1.0f / (1.0f - sg);
+    const float g = 1.0f - sg_next;
+    const bool noisy = eta != 0.0f && g != 0.0f;
+    const float ca = sqrtf(1.0f - eta * eta) - 1.0f;
+    const bool paired = use_cfg || share_halves;
+    const int64_t total = (int64_t)(paired ? n_frames / 2 : n_frames) * elems;
+    const int64_t blocks = (total + 3) >> 2;
+    const bool x1 = pred_type == VGPT_PRED_X1;
+    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < blocks; b += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t e = b << 2, eu = e + total;
+        const int cnt = VEC ? 4 : (int)(total - e < 4 ? total - e : 4);
+        float eps[4] = {0.f, 0.f, 0.f, 0.f};
+        if (noisy) sde_normals(rng, b, st, eps);
+        float zc[4] = {}, zu[4] = {}, pc[4] = {}, pu[4] = {};
+        if (VEC) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(z + e);
+            const bf16x4 p = *reinterpret_cast<const bf16x4*>(pred + e);
+#pragma unroll
+            for (int l = 0; l < 4; ++l) { zc[l] = a[l]; pc[l] = bf2f(p[l]); }
+            if (paired) {
+                const f32x4 c = *reinterpret_cast<const f32x4*>(z + eu);
+#pragma unroll
+                for (int l = 0; l < 4; ++l) zu[l] = c[l];
+            }
+            if (guided || !use_cfg) {
+                if (paired) {
+                    const bf16x4 q = *reinterpret_cast<const bf16x4*>(pred + eu);
+#pragma unroll
+                    for (int l = 0; l < 4; ++l) pu[l] = bf2f(q[l]);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                if (l >= cnt) continue;
+                zc[l] = z[e + l];
+                pc[l] = bf2f(pred[e + l]);
+                if (paired) {
+                    zu[l] = z[eu + l];
+                    if (guided || !use_cfg) pu[l] = bf2f(pred[eu + l]);
+                }
+            }
+        }
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            if (l >= cnt) continue;
+            float vc = pc[l];
+            if (x1) vc = (vc - zc[l]) * inv;
+            float vs = vc;   // the velocity of the paired frame: the guided one under CFG, its own prediction's otherwise
+            if (use_cfg) {
+                if (guided) {
+                    float vu = pu[l];
+                    if (x1) vu = (vu - zu[l]) * inv;
+                    vc = __builtin_fmaf(cfg_scale, vc - vu, vu);
+                }
+                vs = vc;
+            } else if (paired) {
+                vs = pu[l];
+                if (x1) vs = (vs - zu[l]) * inv;
+            }
+            float zn = zc[l] + dt * vc;
+            if (noisy) zn = __builtin_fmaf(g, __builtin_fmaf(eta, eps[l], ca * __builtin_fmaf(-sg, vc, zc[l])), zn);
+            zc[l] = zn;
+            if (paired) {
+                // CFG: the unconditional half moves by fma(h, v, z), as in euler_cfg_kernel; frames that only share
+                // the noise are conditional-shaped elements of their own
+                float zq = use_cfg ? __builtin_fmaf(dt, vs, zu[l]) : zu[l] + dt * vs;
+                if (noisy) zq = __builtin_fmaf(g, __builtin_fmaf(eta, eps[l], ca * __builtin_fmaf(-sg, vs, zu[l])), zq);
+                zu[l] = zq;
+            }
+        }
+        if (VEC) {
+            f32x4 a;
+            bf16x4 p;
+#pragma unroll
+            for (int l = 0; l < 4; ++l) { a[l] = zc[l]; p[l] = f2bf(zc[l]); }
+            *reinterpret_cast<f32x4*>(z + e) = a;
+            *reinterpret_cast<bf16x4*>(zm + e) = p;
+            if (paired) {
+#pragma unroll
+                for (int l = 0; l < 4; ++l) { a[l] = zu[l]; p[l] = f2bf(zu[l]); }
+                *reinterpret_cast<f32x4*>(z + eu) = a;
+                *reinterpret_cast<bf16x4*>(zm + eu) = p;
+            }
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                if (l >= cnt) continue;
+                z[e + l] = zc[l];
+                zm[e + l] = f2bf(zc[l]);
+                if (paired) {
+                    z[eu + l] = zu[l];
+                    zm[eu + l] = f2bf(zu[l]);
+                }
+            }
+        }
+    }
+}
+
 __global__ void advance_kernel(int32_t* step) { *step += 1; }
 
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ src,
@@ -640,6 +825,50 @@ VGPT_EXPORT int vgpt_sampler_update_sched(float* z, void* z_model, const void* p
     else SUS_LAUNCH(2);
 #undef SUS_LAUNCH
     VGPT_CHECK_LAUNCH("vgpt_sampler_update_sched");
+    return VGPT_OK;
+}
+
+VGPT_EXPORT int vgpt_sampler_update_sde(float* z, void* z_model, const void* pred, const float* sigma,
+                                        const float* cfg_table, const float* eta_table, const int64_t* rng,
+                                        const int32_t* step, int n_steps, int n_frames, int64_t elems, int pred_type,
+                                        int use_cfg, float cfg_scale, int share_halves, void* stream) {
+    VGPT_REQUIRE(z && z_model && pred && sigma && eta_table && rng && step, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update_sde: null pointer (z %p, z_model %p, pred %p, sigma %p, eta_table %p, rng %p, step %p)",
+                 (void*)z, z_model, pred, (const void*)sigma, (const void*)eta_table, (const void*)rng, (const void*)step);
+    VGPT_REQUIRE(n_steps > 0, VGPT_ERR_INVALID, "vgpt_sampler_update_sde: n_steps %d <= 0", n_steps);
+    VGPT_REQUIRE(n_frames >= 0 && elems >= 0, VGPT_ERR_INVALID, "vgpt_sampler_update_sde: bad shape (%d frames of %lld)",
+                 n_frames, (long long)elems);
+    VGPT_REQUIRE(pred_type == VGPT_PRED_V || pred_type == VGPT_PRED_X1, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update_sde: unknown prediction type %d", pred_type);
+    VGPT_REQUIRE(!cfg_table || use_cfg, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update_sde: cfg_table %p with use_cfg %d (a guidance table is CFG by definition)",
+                 (const void*)cfg_table, use_cfg);
+    VGPT_REQUIRE(!(use_cfg || share_halves) || n_frames % 2 == 0, VGPT_ERR_INVALID,
+                 "vgpt_sampler_update_sde: use_cfg %d / share_halves %d need an even number of frames (got %d)", use_cfg,
+                 share_halves, n_frames);
+    if (n_frames == 0 || elems == 0) return VGPT_OK;
+    const int64_t total = (int64_t)(use_cfg || share_halves ? n_frames / 2 : n_frames) * elems;
+    const int grid = (int)std::min<int64_t>(cdiv(cdiv(total, 4), 256), 2048);
+    const bool vec = total % 4 == 0 && (uintptr_t)z % 16 == 0 && (uintptr_t)z_model % 8 == 0 && (uintptr_t)pred % 8 == 0;
+#define SDE_LAUNCH(VEC)                                                                                              \
+    hipLaunchKernelGGL(sde_update_kernel<VEC>, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, (bf16*)z_model,     \
+                       (const bf16*)pred, sigma, cfg_table, eta_table, rng, step, n_steps, n_frames, elems, pred_type, \
+                       use_cfg ? 1 : 0, cfg_scale, share_halves ? 1 : 0)
+    if (vec) SDE_LAUNCH(true);
+    else SDE_LAUNCH(false);
+#undef SDE_LAUNCH
+    VGPT_CHECK_LAUNCH("vgpt_sampler_update_sde");
+    return VGPT_OK;
+}
+
+VGPT_EXPORT int vgpt_sampler_noise_fill(float* out, int64_t n, const int64_t* rng, int step_index, void* stream) {
+    VGPT_REQUIRE(out && rng, VGPT_ERR_INVALID, "vgpt_sampler_noise_fill: null pointer (out %p, rng %p)", (void*)out,
+                 (const void*)rng);
+    VGPT_REQUIRE(n >= 0, VGPT_ERR_INVALID, "vgpt_sampler_noise_fill: n %lld < 0", (long long)n);
+    if (n == 0) return VGPT_OK;
+    const int grid = (int)std::min<int64_t>(cdiv(cdiv(n, 4), 256), 2048);
+    hipLaunchKernelGGL(noise_fill_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, n, rng, step_index);
+    VGPT_CHECK_LAUNCH("vgpt_sampler_noise_fill");
     return VGPT_OK;
 }
 

@@ -77,9 +77,11 @@ class StaticDenoiser:
                  reuse_condition_prefix: bool = False, hoist_special_rows: bool = True,
                  attention_precision: str = "bf16", fuse_norms: Optional[bool] = None, linear_precision: str = "bf16",
                  sequence_parallel: bool = False, sp_group=None, solver: str = "euler", guidance_scales=None,
-                 skip_unguided_branch: Optional[bool] = None):
+                 skip_unguided_branch: Optional[bool] = None, eta_table=None):
         # solver: "euler" (default), "ab2" or "heun" (DESIGN.md section 5); an unknown name is refused, naming it, before
         # anything else is looked at
+        # eta_table: None, or one eta in [0, 1] per step (scheduler.eta_table): stochastic Euler steps
+        # whose noise key is set per clip with set_noise_seed() -- see _set_eta
         self.solver = ops.solver_id(solver)
         model._check_ready()
         # fuse_norms: the two RMSNorms of a decoder layer folded into the GEMMs around them in the per-step forward (ops:
@@ -185,6 +187,7 @@ class StaticDenoiser:
         self._set_projection_mode(fuse_norms)
         self._alloc_step_buffers()
         self._set_guidance(guidance_scales, skip_unguided_branch, plan)
+        self._set_eta(eta_table, solver)
         self._initial_passes()
 
     # ---- allocation, once per engine ------------------------------------------------------------------------------------
@@ -292,6 +295,39 @@ class StaticDenoiser:
             # finite
             self.qkv.zero_()
         self.cr = c
+
+    # ---- stochastic steps -------------------------------------------------------------------------
+    def _set_eta(self, table, solver):
+        """eta_table: None (the deterministic sampler: nothing here changes what is launched), or one eta in [0, 1] per step
+        (scheduler.eta_table).  The table and the {seed, stream} pair live at stable device addresses; the update launch of
+        every step -- eager or captured -- reads its eta by the device step counter and its noise key from `rng`, so one
+        engine and its graphs serve every seed (set_noise_seed).  The noise is counter-based: a function of (seed, stream,
+        step, element) that every rank of a sharded engine computes alike on its replicated state."""
+        self.etable, self.rng = None, None
+        if table is None:
+            return
+        t = torch.as_tensor(table, dtype=torch.float32).reshape(-1).cpu()
+        if self.sigma is not None and t.numel() != self.num_steps:
+            raise VgptError(f"StaticDenoiser: eta_table holds {t.numel()} entries, the sigma table has {self.num_steps} steps")
+        bad = [(i, v) for i, v in enumerate(t.tolist()) if not 0.0 <= v <= 1.0]
+        if bad:
+            raise VgptError(f"StaticDenoiser: eta={bad[0][1]!r} at step {bad[0][0]} is outside [0, 1]")
+        noisy = [(i, v) for i, v in enumerate(t.tolist()) if v != 0.0]
+        if noisy and self.solver != ops.SOLVER_EULER:
+            raise VgptError(f"StaticDenoiser: solver={solver!r} with eta={noisy[0][1]!r} at step {noisy[0][0]}: only "
+                            "solver='euler' takes a non-zero eta")
+        if self.solver != ops.SOLVER_EULER:
+            return   # an all-zero table under ab2 / heun: their own updates, untouched
+        self.etable = t.to(self.dev).contiguous()
+        self.rng = torch.zeros(2, dtype=torch.int64, device=self.dev)
+
+    def set_noise_seed(self, seed: int, stream: int = 0):
+        """The noise key of the next clip: per clip, next to set_latents.  Writes the device buffer the update kernel reads;
+        captured graphs are not touched."""
+        if self.rng is None:
+            raise VgptError("StaticDenoiser.set_noise_seed: this engine has no eta_table (nothing is stochastic)")
+        self.rng.copy_(ops.noise_rng(seed, stream, "cpu"), non_blocking=False)
+        return self
 
     def step_rows(self, index: int) -> int:
         """Live rows step `index` of the table computes: the conditional rows in an unguided step of an engine that skips,
@@ -860,6 +896,13 @@ class StaticDenoiser:
         index i + 1 <= N - 1; the final step (sigma[N] = 1) is the Euler-shaped one."""
         ops.sampler_set_timesteps(self.sigma, self.step, self.ts)
         self.forward_step(from_tables=True, cond=cond)
+        if self.etable is not None:
+            # stochastic steps (Euler only): one update kernel that reads the step's eta -- and, under a guidance schedule,
+            # its scale -- by the step counter, and makes its noise from (seed, stream, step, element)
+            ops.sampler_update_sde(self.z, self.z_model, self.pred, self.sigma, self.gtable, self.etable, self.rng, self.step,
+                                   self.pred_type, self.use_cfg, self.cfg_scale, share_halves=self.use_cfg)
+            ops.sampler_advance(self.step)
+            return
         if self.gtable is not None:
             # a guidance schedule: the same steps with the update that reads the step's scale from the table.  cond: an
             # unguided step on the conditional rows only -- both model calls of a Heun step are of the step's kind

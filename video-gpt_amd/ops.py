@@ -938,6 +938,51 @@ def sampler_update_sched(z: torch.Tensor, z_model: torch.Tensor, pred: torch.Ten
          int(stage), _stream())
 
 
+def noise_rng(seed: int, stream: int, device) -> torch.Tensor:
+    """The int64[2] {seed, stream} buffer the stochastic update and noise_fill read on the device.  Both are taken modulo
+    2^64 (the key is the seed's two 32-bit words; of the stream the low word is used)."""
+    wrap = lambda v: ((int(v) + (1 << 63)) % (1 << 64)) - (1 << 63)
+    return torch.tensor([wrap(seed), wrap(stream)], dtype=torch.int64, device=device)
+
+
+def sampler_update_sde(z: torch.Tensor, z_model: torch.Tensor, pred: torch.Tensor, sigma: torch.Tensor,
+                       cfg_table: Optional[torch.Tensor], eta_table: torch.Tensor, rng: torch.Tensor, step: torch.Tensor,
+                       pred_type: int, use_cfg: bool, cfg_scale: float, share_halves: bool = False):
+    """One Euler step with noise re-injected (include/vgpt.h: vgpt_sampler_update_sde).  eta_table:
+    fp32, one entry per step of sigma's table; rng: int64[2] {seed, stream} on z's device (noise_rng); cfg_table: None, or
+    the per-step guidance scales of sampler_update_sched (needs use_cfg)."""
+    _chk(z, torch.float32, "sampler_update_sde.z"); _chk(z_model, BF16, "sampler_update_sde.z_model")
+    _chk(pred, BF16, "sampler_update_sde.pred"); _chk(eta_table, torch.float32, "sampler_update_sde.eta_table")
+    _chk(rng, torch.int64, "sampler_update_sde.rng")
+    nf = z.shape[0]
+    if z_model.numel() != z.numel() or pred.numel() != z.numel():
+        raise VgptError(f"sampler_update_sde: z_model ({z_model.numel()}) / pred ({pred.numel()}) are not z's "
+                        f"{z.numel()} elements")
+    if eta_table.numel() != sigma.numel() - 1:
+        raise VgptError(f"sampler_update_sde: eta_table holds {eta_table.numel()} entries, the sigma table has "
+                        f"{sigma.numel() - 1} steps")
+    if rng.numel() != 2:
+        raise VgptError(f"sampler_update_sde: rng holds {rng.numel()} values, not {{seed, stream}}")
+    if cfg_table is not None:
+        _chk(cfg_table, torch.float32, "sampler_update_sde.cfg_table")
+        if cfg_table.numel() != sigma.numel() - 1:
+            raise VgptError(f"sampler_update_sde: cfg_table holds {cfg_table.numel()} scales, the sigma table has "
+                            f"{sigma.numel() - 1} steps")
+    call("vgpt_sampler_update_sde", z.data_ptr(), z_model.data_ptr(), pred.data_ptr(), sigma.data_ptr(), _ptr(cfg_table),
+         eta_table.data_ptr(), rng.data_ptr(), step.data_ptr(), sigma.numel() - 1, nf, z.numel() // max(nf, 1), pred_type,
+         int(bool(use_cfg)), float(cfg_scale), int(bool(share_halves)), _stream())
+
+
+def sampler_noise_fill(out: torch.Tensor, rng: torch.Tensor, step_index: int) -> torch.Tensor:
+    """out[e] = the standard normal of (seed, stream, step_index, e): the stochastic update's noise on its own
+    (include/vgpt.h: vgpt_sampler_noise_fill).  out: fp32, contiguous; rng: int64[2] {seed, stream} on out's device."""
+    _chk(out, torch.float32, "sampler_noise_fill.out"); _chk(rng, torch.int64, "sampler_noise_fill.rng")
+    if rng.numel() != 2:
+        raise VgptError(f"sampler_noise_fill: rng holds {rng.numel()} values, not {{seed, stream}}")
+    call("vgpt_sampler_noise_fill", out.data_ptr(), out.numel(), rng.data_ptr(), int(step_index), _stream())
+    return out
+
+
 def sampler_copy_step_rows(src: torch.Tensor, dst: torch.Tensor, step: torch.Tensor):
     """src: (n_steps, n_layers, rows, W) contiguous; dst: a (n_layers, rows, W) VIEW whose rows are contiguous (layer
     stride arbitrary).  dst[l] = src[*step][l]."""

@@ -50,6 +50,12 @@ class LVMPipeline:
         # schedule and runs as it always did; the scheduler, asked directly for a schedule without CFG, refuses
         self.guidance_interval = None
         self.guidance_schedule = None
+        # stochastic sampler steps (scheduler.eta_table): eta in [0, 1] inside the sigma interval
+        # `eta_interval` = (lo, hi), or at every step without one; 0 = the deterministic sampler.  The noise of a round is
+        # keyed by the call's `seed` (0 when None) and the round's index, so the rounds of a rollout do not repeat each
+        # other's noise although their initial latents are re-seeded alike
+        self.eta = 0.0
+        self.eta_interval = None
 
     @classmethod
     def from_pretrained(cls, model_name, vae_path: str = None, load_llm_ckpt=True):
@@ -209,7 +215,9 @@ class LVMPipeline:
             scheduler = LVMScheduler(num_steps=num_inference_steps, time_shifting_factor=time_shifting_factor,
                                      solver=self.solver,
                                      guidance_interval=self.guidance_interval if use_img_guidance else None,
-                                     guidance_schedule=self.guidance_schedule if use_img_guidance else None)
+                                     guidance_schedule=self.guidance_schedule if use_img_guidance else None,
+                                     eta=self.eta, eta_interval=self.eta_interval,
+                                     noise_seed=0 if seed is None else seed, noise_stream=gen_idx)
             scheduler.attention_precision = self.attention_precision
             scheduler.linear_precision = self.linear_precision
             scheduler.sequence_parallel_engine = self.sequence_parallel_engine
@@ -320,7 +328,9 @@ class LVMPipeline:
             scheduler = LVMScheduler(num_steps=num_inference_steps, time_shifting_factor=time_shifting_factor,
                                      solver=self.solver,
                                      guidance_interval=self.guidance_interval if use_img_guidance else None,
-                                     guidance_schedule=self.guidance_schedule if use_img_guidance else None)
+                                     guidance_schedule=self.guidance_schedule if use_img_guidance else None,
+                                     eta=self.eta, eta_interval=self.eta_interval,
+                                     noise_seed=0 if seed is None else seed, noise_stream=k)
             scheduler.attention_precision = self.attention_precision
             scheduler.linear_precision = self.linear_precision
             scheduler.sequence_parallel_engine = self.sequence_parallel_engine

@@ -1,6 +1,8 @@
 """LVMScheduler: rectified-flow sampler (mirror of LVM/scheduler.py:119-208: first-order Euler, the default), with two
 second-order solvers beside it (`solver="ab2"`: two-step Adams-Bashforth, one model call per step; `solver="heun"`:
-2 N - 1 model calls for N steps; arithmetic in DESIGN.md section 5).
+2 N - 1 model calls for N steps; arithmetic in DESIGN.md section 5), and stochastic Euler steps (`eta` in (0, 1]: the
+flow-matching counterpart of DDIM's eta -- fresh counter-based noise re-injected at every step inside the update kernel;
+DESIGN.md section 5c).
 
 `__call__(z, func, model_kwargs, ...)` keeps the reference contract:
 `func(z, timesteps, past_key_values=None, prediction_type=..., **model_kwargs) -> (pred, cache)`.
@@ -61,11 +63,53 @@ def guidance_table(sigma, scale: float, interval=None, schedule=None):
     return out
 
 
+def eta_table(sigma, eta: float, interval=None):
+    """The stochasticity of every step of the table `sigma` (N + 1 entries, step i runs at sigma[i]) as an fp32 tensor (N),
+    or None when eta == 0: the deterministic sampler.  Entry i is `eta` where lo <= sigma[i] < hi of `interval` = (lo, hi),
+    in the scheduler's own sigma units (0 = noise, 1 = data), and 0 elsewhere; without an interval every step gets `eta`.
+    A step with eta_i in (0, 1] replaces that share of the state's noise part by fresh noise:
+    z' = (z + h v) + (1 - sigma[i+1]) ((sqrt(1 - eta_i^2) - 1) x0_hat + eta_i eps), x0_hat = z - sigma[i] v."""
+    e = float(eta)
+    if not 0.0 <= e <= 1.0:   # also refuses a NaN
+        raise VgptError(f"eta_table: eta={eta!r} is outside [0, 1]")
+    lo = hi = None
+    if interval is not None:
+        lo, hi = (float(v) for v in interval)
+        if not lo <= hi:   # also refuses a NaN bound
+            raise VgptError(f"eta_table: interval lo={lo!r} > hi={hi!r}")
+    if e == 0.0:
+        return None
+    sig = [float(s) for s in torch.as_tensor(sigma).reshape(-1).tolist()]
+    n = len(sig) - 1
+    if n <= 0:
+        raise VgptError(f"eta_table: a sigma table of {len(sig)} entries has no step")
+    return torch.tensor([e if lo is None or lo <= s < hi else 0.0 for s in sig[:n]], dtype=torch.float32)
+
+
+def refuse_noisy_solver(who: str, solver: str, table):
+    """Only the first-order step takes noise: a multistep history is meaningless across injected noise."""
+    if table is None or solver == "euler":
+        return
+    bad = [(i, v) for i, v in enumerate(torch.as_tensor(table).reshape(-1).tolist()) if v != 0.0]
+    if bad:
+        raise VgptError(f"{who}: solver={solver!r} with eta={bad[0][1]!r} at step {bad[0][0]}: only solver='euler' takes a "
+                        "non-zero eta")
+
+
 class LVMScheduler:
     def __init__(self, num_steps: int = 50, time_shifting_factor: int = 1, begin_time=None, solver: str = "euler",
-                 guidance_interval=None, guidance_schedule=None):
+                 guidance_interval=None, guidance_schedule=None, eta: float = 0.0, eta_interval=None, noise_seed: int = 0,
+                 noise_stream: int = 0):
         ops.solver_id(solver)   # an unknown name is refused here, naming it
         self.solver = solver
+        # stochastic steps (eta_table, DESIGN.md section 5c): eta in [0, 1] inside `eta_interval` = (lo, hi) of sigma (every
+        # step without one), 0 = the deterministic sampler, bit for bit.  The noise is counter-based, a function of
+        # (noise_seed, noise_stream, step, element) computed in the update kernel: seed and stream live in device memory, so
+        # a cached engine and its captured graphs serve any of them
+        self.eta = eta
+        self.eta_interval = eta_interval
+        self.noise_seed = noise_seed
+        self.noise_stream = noise_stream
         # a per-step image-CFG scale (guidance_table): the clip's img_cfg_scale inside `guidance_interval` = (lo, hi) of
         # sigma and 1.0 outside it, or `guidance_schedule` (num_steps scales, or a callable of sigma_i).  Both None: one
         # scale for the clip, as before.  The fast path skips the unconditional rows in the steps whose scale is exactly 1
@@ -79,6 +123,7 @@ class LVMScheduler:
         t = torch.linspace(0 if begin_time is None else begin_time, 1, num_steps + 1)
         self.sigma = t / (t + time_shifting_factor - time_shifting_factor * t)
         guidance_table(self.sigma, 1.0, guidance_interval, guidance_schedule)   # a bad schedule is refused here, by value
+        refuse_noisy_solver("LVMScheduler", solver, eta_table(self.sigma, eta, eta_interval))   # so is a bad eta
         self.use_graph = True
         self.pack_padding = True
         self.reuse_condition_prefix = True   # compute the step-invariant condition rows once per clip (engine.py)
@@ -120,14 +165,20 @@ class LVMScheduler:
         wait_for_pending_update(owner)      # a trainer's overlapped AdamW update of these parameters may still be in flight
         self._owner_params = list(owner.parameters())
         self._table = self._guidance(model_kwargs)
+        self._eta = self._eta_table()
         key = self._engine_key(z, model_kwargs, prediction_type) if self.cache_engines else None
         cache = owner.__dict__.setdefault("_vgpt_engine_cache", {}) if key is not None else None
         if cache is not None and key in cache:
             eng = cache.pop(key)
             cache[key] = eng                     # most recently used last
             self.last_engine_reused = True
-            return eng.rebind(lat)
+            eng = eng.rebind(lat)
+            if self._eta is not None:
+                eng.set_noise_seed(self.noise_seed, self.noise_stream)
+            return eng
         eng = self._build_engine(StaticDenoiser, owner, z, lat, model_kwargs, prediction_type)
+        if self._eta is not None:
+            eng.set_noise_seed(self.noise_seed, self.noise_stream)
         if cache is not None:
             cache[key] = eng
             while len(cache) > 2:                # a clip's buffers are a few GB at cfg-2: the last two layouts are kept
@@ -143,6 +194,14 @@ class LVMScheduler:
                             f"{self.guidance_schedule!r} with use_img_cfg=False: there is nothing to schedule")
         return guidance_table(self.sigma, float(model_kwargs.get("img_cfg_scale", 1.0)), self.guidance_interval,
                               self.guidance_schedule)
+
+    def _eta_table(self):
+        """The clip's eta table (eta_table on this scheduler's sigma), or None: the deterministic sampler."""
+        table = eta_table(self.sigma, self.eta, self.eta_interval)
+        refuse_noisy_solver("LVMScheduler", self.solver, table)
+        if table is not None and not bool((table != 0).any()):
+            return None   # an interval that covers no step: nothing is stochastic, the old path and its engine
+        return table
 
     def _engine_key(self, z, model_kwargs, prediction_type):
         """Everything a StaticDenoiser is built from except the condition latents' VALUES; None when the mask is not a
@@ -162,6 +221,8 @@ class LVMScheduler:
                 self.linear_precision, self.fuse_norms, str(z[0].device), self.solver,
                 # two guidance schedules never share an engine: its table, step kinds and graphs are the schedule's
                 None if self._table is None else self._table.numpy().tobytes(), self.skip_unguided_branch,
+                # nor two eta tables; the noise seed and stream are NOT here: the engine reads them from device memory
+                None if self._eta is None else self._eta.numpy().tobytes(),
                 # a sharded engine holds this rank's rows and heads of a group of this size
                 self.sequence_parallel_engine, SPM.sp_world(), SPM.sp_rank(),
                 # the GEMM family decided whether the engine folded the RMSNorms (norm_workspace_bytes is 0 under family 1) and
@@ -182,7 +243,7 @@ class LVMScheduler:
                               attention_precision=self.attention_precision, linear_precision=self.linear_precision,
                               fuse_norms=self.fuse_norms, sequence_parallel=self.sequence_parallel_engine,
                               solver=self.solver, guidance_scales=self._table,
-                              skip_unguided_branch=self.skip_unguided_branch)
+                              skip_unguided_branch=self.skip_unguided_branch, eta_table=self._eta)
 
     def __call__(self, z, func, model_kwargs, use_kv_cache: bool = True, offload_kv_cache: bool = True,
                  prediction_type: str = "v", vae=None, noise_level=None):
@@ -260,6 +321,13 @@ class LVMScheduler:
         scales = None if table is None else table.tolist()
         table_dev = table.to(dev) if kernel_cfg and table is not None else None
         # the guided velocity of the step (ab2: of the previous one when it is read), one CFG half
+        # stochastic steps: the same update with the step's eta and counter-based noise.  Under CFG both halves get the same
+        # noise, also where func combined them itself (v predictions: share_halves)
+        eta_tab = self._eta_table()
+        if eta_tab is not None:
+            eta_dev = eta_tab.to(dev)
+            rng = ops.noise_rng(self.noise_seed, self.noise_stream, dev)
+            share = use_cfg and n % 2 == 0
         v_hist = None if solver == ops.SOLVER_EULER else torch.empty(n // 2 if kernel_cfg else n, elems, dtype=torch.float32,
                                                                     device=dev)
 
@@ -287,7 +355,9 @@ class LVMScheduler:
                 ops.sampler_advance(step)
                 update(evaluate(i), 1)
                 continue
-            if solver == ops.SOLVER_AB2 or table_dev is not None:
+            if eta_tab is not None:
+                ops.sampler_update_sde(zf, zm, pred, sigma, table_dev, eta_dev, rng, step, pred_type, kernel_cfg, scale, share)
+            elif solver == ops.SOLVER_AB2 or table_dev is not None:
                 update(pred)
             else:
                 ops.euler_cfg_update(zf, zm, pred, sigma, step, pred_type, kernel_cfg, scale)
